@@ -13,14 +13,20 @@ batch of its own; `--scaling strong`: ONE unit list is cut into contiguous range
 (swcompression_amd/shard.py) and every rank decodes its range.  RCCL carries only the barrier, the max-over-ranks time
 and the byte totals.
 
-Prints ONE compact JSON line (< 4 KB, `compact_line`; the whole object goes to bench_full.json): decompressed GiB/s (sum of U over all ranks / max time), plus
+A plain run does only what the headline needs: set-up, `--warmup` steps, `--steps` timed steps, the outputs of the last
+timed step if `--dump-outputs DIR` is given, and the result line (decompressed GiB/s = sum of U over all ranks / max
+time, `ms_per_step`, and the roofline of the timed launches).  `--full` adds everything else below: the device
+verification of every unit, the per-kernel timing launches, the CPU baselines, configs[0], the archive paths, per_codec
+and the streamed LZ4 mode, and writes the whole object to bench_full.json.
+
+Prints ONE compact JSON line (< 4 KB, `compact_line`; with --full the whole object goes to bench_full.json), plus
   roofline     -- HBM roofline of the headline: algorithmic bytes (C + U per unit) / mean duration of a
-                  launch, measured with HIP events on the launch stream (per kernel for the Deflate kernels), vs 8 TB/s;
+                  launch, measured with HIP events on the launch stream (per kernel for the Deflate kernels, --full), vs 8 TB/s;
                   `traffic` / `l2_hit_rate` = HBM bytes per launch and TCC_HIT / (TCC_HIT + TCC_MISS) per kernel from the
                   committed rocprofv3 --pmc passes of this same command (profiles/*_traffic.json), or null;
-  cpu_baseline -- the CPU oracle (a port of the reference's algorithm) timed on a bounded sample of the same workload
-                  on this box's host cores (rank 0, N = 1 only);
-  per_codec    -- (N = 1) the other BASELINE configs on their stated sizes -- LZ4 8,192 x 4 MiB, BZip2 10,240 x 900 kB,
+  cpu_baseline -- (--full) the CPU oracle (a port of the reference's algorithm) timed on a bounded sample of the same
+                  workload on this box's host cores (rank 0, N = 1 only);
+  per_codec    -- (--full, N = 1) the other BASELINE configs on their stated sizes -- LZ4 8,192 x 4 MiB, BZip2 10,240 x 900 kB,
                   LZMA2 32,768 x 256 KiB -- each with value / roofline / cpu_baseline, every unit verified on the device.
 `--workload X` times workload X alone as the headline line.
 """
@@ -146,6 +152,11 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: verification of every unit, per-kernel timing, CPU baselines, configs[0], "
+                         "archive paths, per_codec, streamed LZ4, bench_full.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64; a seeded sample of the output bytes)")
     ap.add_argument("--workload", default="deflate64k", choices=sorted(WORKLOADS))
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the batch (debug only; <1 is not a valid headline run)")
@@ -159,7 +170,10 @@ def parse_args():
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="multi-rank REHEARSAL on a box with one GPU: all ranks share cuda:0 and the bookkeeping collectives run over gloo "
                          "(exercises sharding, barriers and the max-over-ranks clock; the figure it prints is not a scaling result)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def scaled_parts(w, scale, override=None):
@@ -594,7 +608,37 @@ def verify_all_units(name, batch, raw, plains, trailers):
     return {"units_verified": int(batch.n), "method": how}
 
 
-def run_workload(name, args, lib, torch, dist, world, rank, device, steps, warmup, with_cpu):
+DUMP_LIMIT = 60 * 10**6          # bytes of .npy data that --dump-outputs may write in all
+DUMP_SAMPLE_SEED = 0x5C0DE
+
+
+def dump_outputs(out_dir, batch, gzip_crc):
+    """--dump-outputs: what a caller of the timed path receives from the LAST timed step (the step after wipe_results),
+    as .npy files -- every job's status, out_len and in_consumed, the device CRC-32 of every member where the step
+    computes it (gzip), and the output bytes of a fixed, seeded sample of jobs, one zero-padded row per job."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    r = batch.results()
+    arrays = {"status": r["status"].astype(np.float64), "out_len": r["out_len"].astype(np.float64),
+              "in_consumed": r["in_consumed"].astype(np.float64)}
+    if gzip_crc:
+        arrays["crc32"] = batch._crc_buf.cpu().numpy().view(np.uint32).astype(np.float64)
+    cap = int(batch.caps.max())
+    budget = DUMP_LIMIT - sum(a.nbytes for a in arrays.values())
+    k = max(1, min(batch.n, budget // (4 * cap + 8)))
+    jobs = np.sort(np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED)).choice(batch.n, size=k, replace=False))
+    rows = np.zeros((k, cap), dtype=np.float32)
+    for row, i in zip(rows, jobs):
+        n = int(min(r["out_len"][i], r["out_cap"][i]))
+        o = int(batch._out_off[i])
+        row[:n] = batch.d_out[o:o + n].cpu().numpy()
+    arrays["output_sample"] = rows
+    arrays["output_sample_jobs"] = jobs.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def run_workload(name, args, lib, torch, dist, world, rank, device, steps, warmup, with_cpu, full=True, dump_dir=None):
     w = WORKLOADS[name]
     parts = scaled_parts(w, args.scale, args.parts if name == args.workload else None)
     n_distinct = sum(n for _, n in parts)
@@ -665,30 +709,38 @@ def run_workload(name, args, lib, torch, dist, world, rank, device, steps, warmu
     else:
         dt_max, tot_u = dt, float(sum_u)
 
+    # the outputs of the LAST timed step, before anything else launches
+    if dump_dir:
+        dump_outputs(dump_dir, batch, gzip_crc)
+
     # every unit of the LAST timed step is checked before anything else launches (the phase-timing launches below rewrite
     # all outputs: checking after them would check them)
-    if name == "lz4_compress_4m":
-        verify = verify_compressed_units(batch, plains, torch)
-    elif name == "deflate_compress_64k":
-        verify = verify_compressed_units(batch, plains, torch, codec="deflate")
-    else:
-        verify = verify_all_units(name, batch, raw, plains, trailers)
+    verify = None
+    if full:
+        if name == "lz4_compress_4m":
+            verify = verify_compressed_units(batch, plains, torch)
+        elif name == "deflate_compress_64k":
+            verify = verify_compressed_units(batch, plains, torch, codec="deflate")
+        else:
+            verify = verify_all_units(name, batch, raw, plains, trailers)
 
     # outside the timed region: per-kernel durations of more launches (HIP events inside the library, on the launch stream)
-    lib.swc_set_tuning(b"phase_timing", 1)
+    phases = None
     names = w["kernels"]
-    acc = [0.0] * len(names)
     reps = 3 if gzip_crc else 1
-    got = 0
-    for _ in range(reps):
-        batch.launch(sync=True)
-        buf = (C.c_float * 8)()
-        if lib.swc_last_phase_ms(buf, 8) == len(names):
-            got += 1
-            for i in range(len(names)):
-                acc[i] += buf[i]
-    lib.swc_set_tuning(b"phase_timing", 0)
-    phases = {n + "_ms": a / got for n, a in zip(names, acc)} if got else None
+    if full:
+        lib.swc_set_tuning(b"phase_timing", 1)
+        acc = [0.0] * len(names)
+        got = 0
+        for _ in range(reps):
+            batch.launch(sync=True)
+            buf = (C.c_float * 8)()
+            if lib.swc_last_phase_ms(buf, 8) == len(names):
+                got += 1
+                for i in range(len(names)):
+                    acc[i] += buf[i]
+        lib.swc_set_tuning(b"phase_timing", 0)
+        phases = {n + "_ms": a / got for n, a in zip(names, acc)} if got else None
     if phases is not None and gzip_crc:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -722,7 +774,9 @@ def run_workload(name, args, lib, torch, dist, world, rank, device, steps, warmu
                       "compressed_bytes_per_gpu": sum_c, "decompressed_bytes_per_gpu": sum_u,
                       "payload_classes": dict(parts), "payload": PAYLOAD_NOTE,
                       "parallelism": "%d x independent shards (%s scaling)" % (world, args.scaling)},
-           "roofline": roof, "verify": verify, "stats": stats(launch_ms, warmup)}
+           "roofline": roof, "stats": stats(launch_ms, warmup)}
+    if verify is not None:
+        res["verify"] = verify
     if with_cpu and rank == 0:
         res["cpu_baseline"] = cpu_baseline(name, raw, plains, args.cpu_seconds if name == args.workload else min(args.cpu_seconds, 5.0))
         if name != "deflate64k":   # (the headline's context lines are attached by main())
@@ -830,14 +884,17 @@ def main():
     if args.streamed_only:
         print(json.dumps({"lz4_streamed": run_lz4_streamed(args, torch, device)}))
         return
-    with_cpu = world == 1 and not args.no_cpu_baseline
-    head, batch, raw, plains = run_workload(args.workload, args, lib, torch, dist, world, rank, device, args.steps, args.warmup, with_cpu)
+    with_cpu = args.full and world == 1 and not args.no_cpu_baseline
+    head, batch, raw, plains = run_workload(args.workload, args, lib, torch, dist, world, rank, device, args.steps, args.warmup, with_cpu,
+                                            full=args.full, dump_dir=args.dump_outputs if rank == 0 else None)
     line = None
     if rank == 0:
         line = {"metric": "decompressed GiB/s", "value": head["value"], "unit": "GiB/s", "n_gpus": 1 if args.rehearse_on_one_gpu else world, "steps": args.steps,
                 "warmup": args.warmup, "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": args.scaling,
                 "vs_baseline": None, "dtype": "u8", "data": "synthetic", "config": head["config"], "roofline": head["roofline"],
-                "verify": head["verify"], "stats": head["stats"]}
+                "stats": head["stats"]}
+        if "verify" in head:
+            line["verify"] = head["verify"]
         if args.rehearse_on_one_gpu:
             line["rehearsal"] = True   # all ranks share ONE GPU: exercises the multi-rank contract, not a scaling result
             line["ranks"] = world
@@ -859,7 +916,7 @@ def main():
                     line["archive_paths"] = {"error": str(e)[:200]}
     del batch
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and args.workload == "deflate64k" and not args.no_per_codec and args.scale == 1.0:
+    if args.full and rank == 0 and world == 1 and args.workload == "deflate64k" and not args.no_per_codec and args.scale == 1.0:
         per = {}
         for name in ("deflate64k_mix", "lz4_4m", "bzip2_900k", "lzma2_256k", "lzma2_256k_bin", "lz4_compress_4m", "deflate_compress_64k"):
             res, b, _, _ = run_workload(name, args, lib, torch, dist, world, rank, device, WORKLOADS[name]["steps"], 1, with_cpu)
@@ -876,7 +933,8 @@ def main():
         except Exception as e:   # e.g. not enough pinned host memory on the box: say so instead of dropping the headline
             line["lz4_streamed"] = {"error": str(e)[:200]}
     if rank == 0:
-        line["full"] = write_full(line)
+        if args.full:
+            line["full"] = write_full(line)
         sys.stdout.flush()
         print(compact_line(line), flush=True)
     if world > 1:

@@ -12,7 +12,7 @@ tests)
   python __graft_entry__.py smoke 2>&1 | tail -1 | tee $O/smoke.log ;;
 bench)
   # (stdout's last line is the compact headline object the driver parses; the whole object is written to gpurun_out/bench_full.json by bench.py itself)
-  S=$(date +%s); python bench.py > $O/bench_line.json 2> $O/bench_full.err; echo "bench rc=$? wall=$(( $(date +%s) - S ))s" | tee $O/bench_full.wall
+  S=$(date +%s); python bench.py --full > $O/bench_line.json 2> $O/bench_full.err; echo "bench rc=$? wall=$(( $(date +%s) - S ))s" | tee $O/bench_full.wall
   tail -1 $O/bench_line.json | wc -c; cp gpurun_out/bench_full.json $O/bench_full.json
   python - <<PY
 import json
