@@ -302,11 +302,11 @@ const char* swc_version(void);
  *   "lzma_coder_cache" = 1 | 0  process-wide: LZMA / LZMA2 launches with a workspace keep four LINES (a third of a literal
  *                               coder each) in LDS as a cache of the coders in the workspace (32 streams per CU, default) or
  *                               all coders of lc + lp <= 3 in LDS (10 streams per CU);
- *   "lz_copier" = 1 | 0 | 2 | -1 | -2   process-wide: the LZ77 copy phase of Deflate / LZ4 launches -- 1 (default): one stream
- *                               per wave (csrc/lz_copy.h: Deflate a 6 KiB LDS window in groups of up to 1 KiB, LZ4 9 KiB / 2 KiB)
+ *   "lz_copier" = 1 | 0 | -1    process-wide: the LZ77 copy phase of Deflate / LZ4 launches -- 1 (default): one stream
+ *                               per wave (csrc/lz_copy.h: Deflate a 6 KiB LDS window in groups of up to 1 KiB, LZ4 7 KiB / 1 KiB)
  *                               for launches of 2,560 streams and more, one stream per 512-thread workgroup
- *                               (csrc/lz_resolve.h) below; 0: the workgroup kernel always; 2: Deflate launches take the wave
- *                               kernel with a 16 KiB window; -1 / -2: the wave kernel whatever the launch size;
+ *                               (csrc/lz_resolve.h) below; 0: the workgroup kernel always; -1: the wave kernel whatever the
+ *                               launch size;
  *   "deflate_team" = 1 | 0 | -1 process-wide: Deflate launches of up to 256 streams give every stream a workgroup of six wavefronts
  *                               (csrc/inflate_sync.h: the master on the job, the helpers on the rounds behind the master's --
  *                               the latency of ONE stream is a wave's, and a team cuts it by three) (1, default), one wavefront
@@ -317,8 +317,7 @@ const char* swc_version(void);
  *   "bzip2_team_walk" = 1 | 0 | 2   process-wide: BZip2 launches run stage 3 -- the inverse Burrows-Wheeler walk, the lay-out,
  *                               the RLE1 undo -- as kernels of their own that walk out of the XCDs' L2 (csrc/bzip2_team.h)
  *                               unless the launch is tiny (1, default), never (0: one wavefront takes a block through all
- *                               stages), or always (2);
- *   "bzip2_team_per_cu" = 1 | 2 process-wide: workgroups of the team walk per CU (1, default; 2 for comparison runs). */
+ *                               stages), or always (2). */
 int swc_set_tuning(const char* key, int value);
 /* Profile builds of the library (-DSWC_PROFILE) only: a device buffer of 32 x uint64 per job of the next Deflate
  * launches that the kernels fill with cycle counts per stage (tools/exp_profile.py).  NULL switches it off.  A no-op in
@@ -326,8 +325,8 @@ int swc_set_tuning(const char* key, int value);
 int swc_set_profile_buffer(void* device_ptr);
 /* With "phase_timing" on: durations (ms) of the kernels of the calling thread's last batch launch, in launch order --
  * Deflate: entropy decode, LZ77 resolve; LZ4: dictionary-block kernel, parse, resolve; BZip2: block kernel (Huffman + MTF,
- * counting sort, walk), serial fallback, block CRC; LZMA / LZMA2: the one kernel.  Returns the number of values written
- * (0 if none or if `cap` is too small; at most 4). */
+ * counting sort, walk), with "bzip2_team_walk" the team walk and the team finish, serial fallback, block CRC; LZMA / LZMA2:
+ * the one kernel.  Returns the number of values written (0 if none or if `cap` is too small; at most 5). */
 int swc_last_phase_ms(float* ms, int cap);
 
 /* Process-wide launch statistics of the host framing layer (monotonic, for tests and tuning): "launches" = batched

@@ -437,11 +437,10 @@ int swc_set_tuning(const char* key, int value) try {
     if (!key) return SWC_E_INVALID_ARGUMENT;
     if (!strcmp(key, "phase_timing") && (value == 0 || value == 1)) { set_phase_timing(value); return SWC_OK; }
     if (!strcmp(key, "lzma_coder_cache") && (value == 0 || value == 1)) { set_lzma_coder_cache(value); return SWC_OK; }
-    if (!strcmp(key, "lz_copier") && value >= -2 && value <= 2) { set_lz_copier(value); return SWC_OK; }
+    if (!strcmp(key, "lz_copier") && value >= -1 && value <= 1) { set_lz_copier(value); return SWC_OK; }
     if (!strcmp(key, "deflate_team") && value >= -1 && value <= 1) { set_deflate_team(value); return SWC_OK; }
     if (!strcmp(key, "bzip2_hot_cxx") && (value == 0 || value == 1)) { set_bzip2_hot_cxx(value); return SWC_OK; }
     if (!strcmp(key, "bzip2_team_walk") && value >= 0 && value <= 2) { set_bzip2_team_walk(value); return SWC_OK; }
-    if (!strcmp(key, "bzip2_team_per_cu") && value >= 1 && value <= 2) { set_bzip2_team_per_cu(value); return SWC_OK; }
     if (!strcmp(key, "pinned_keep_mib") && value >= 0) { g_pinned_keep = (size_t)value << 20; return SWC_OK; }
     if (!strcmp(key, "result_cache_mib") && value >= 0) { g_result_cache = (size_t)value << 20; return SWC_OK; }
     if (!strcmp(key, "pool_keep_mib") && value >= 0) {   // applies to the current device at once, to the others when they are first used

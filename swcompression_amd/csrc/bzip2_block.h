@@ -527,7 +527,7 @@ struct Stage1 {
     // every symbol the group still has -- so "is the register full" is never asked per symbol.
     enum { kGroupDone = 0, kSymbol = 1, kIndex = 2 };
     SWC_HD int hot_symbols(Loop& L, int& i, uint32_t& pending, uint32_t& pending_len) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(SWC_BZ_HOT_CXX)
+#if defined(__HIP_DEVICE_COMPILE__)
         if (!CXX) return hot_symbols_isa(L, i, pending, pending_len);
 #endif
         return hot_symbols_cxx(L, i, pending, pending_len);

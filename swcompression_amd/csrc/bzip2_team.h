@@ -247,9 +247,6 @@ SWC_HD void team_finish(Job& job, Workspace ws, FinishLds* l, int lane) {
         if (!(j == j0 && off == n && visited == pieces && seen == segs)) return;   // several cycles: the reference keeps circling the first one
     }
     simt::wave_fence();
-#if defined(SWC_TF_CUT) && SWC_TF_CUT == 1   // (timing experiments only: wrong results)
-    return;
-#endif
     // every segment's offset: the pieces once more
     for (uint32_t j = (uint32_t)lane; j < pieces; j += (uint32_t)WAVE) {
         uint32_t sg = piece_start(j), off = l->o.nx[j];
@@ -261,9 +258,6 @@ SWC_HD void team_finish(Job& job, Workspace ws, FinishLds* l, int lane) {
         }
     }
     simt::vmem_fence();
-#if defined(SWC_TF_CUT) && SWC_TF_CUT == 2
-    return;
-#endif
     // lay out.  The buffered prefixes: eight lanes per segment, eight bytes each per step (a lane per segment would read a line
     // per eight bytes and wait for the longest of 64 segments)
 #ifndef SWC_TF_LPS
@@ -305,9 +299,6 @@ SWC_HD void team_finish(Job& job, Workspace ws, FinishLds* l, int lane) {
     simt::wave_fence();
     const uint32_t n_over = l->n_over;
     if (n_over > kOver) return;                       // (a distribution of segment lengths no data has shown: the serial walk)
-#if defined(SWC_TF_CUT) && SWC_TF_CUT == 3
-    return;
-#endif
     // ... and what lies behind the buffers: a lane per such segment goes on from where the segment's walk had filled its buffer
     for (uint32_t e = (uint32_t)lane; e < n_over; e += (uint32_t)WAVE) {
         const uint32_t q = l->a.over[e], len = (uint32_t)ts.ln[q];
@@ -320,9 +311,6 @@ SWC_HD void team_finish(Job& job, Workspace ws, FinishLds* l, int lane) {
         }
     }
     simt::vmem_fence();
-#if defined(SWC_TF_CUT) && SWC_TF_CUT == 4
-    return;
-#endif
     rle1_undo_to_output<WAVE>(job, ws, n, l->a.part_at, l->a.part_out, lane);
     if (lane == 0) ws.hdr->pad = kWalkDone;
 }

@@ -62,9 +62,6 @@ constexpr uint32_t kPosFail = 0xFFFFFFFFu;
 #define SWC_COPY_REC 16   // records / literal groups (both multiples of four) a lane moves per step of copy_prov
 #define SWC_COPY_LIT 8
 #endif
-#ifndef SWC_WALK_WINDOW
-#define SWC_WALK_WINDOW 0
-#endif
 constexpr uint32_t kSyncWalkBack = SWC_SYNC_WALK_BACK;   // bits
 static_assert(kSyncChunk % 4 == 0 && kSyncChunk >= 36, "sub-chunks are whole dwords");
 
@@ -137,11 +134,8 @@ struct SyncLds {   // 10,240 bytes: see kSyncChunk
     alignas(16) uint8_t stage[kSyncStage];                          // staged input of a round (shifted left by two bits); header build: scratch.  FIRST: the window reads (two dwords at a computed address) then need no base added
     uint32_t lut[(1 << kSyncLitBits) + (1 << kSyncDistBits)];      // direct tables: lit/len, then distance
     uint32_t sub[kSubLds];                                          // subtables of the long codes (if they fit)
-#ifdef SWC_SYNC_LDS_PAD
-    uint8_t occupancy_experiment_pad[SWC_SYNC_LDS_PAD];             // (tools/gpu_chunk_sweep.sh: fewer waves per CU, nothing else changed)
-#endif
 };
-#if SWC_SYNC_CHUNK == 68 && !defined(SWC_SYNC_LDS_PAD) && SWC_SYNC_LIT_BITS == 10
+#if SWC_SYNC_CHUNK == 68 && SWC_SYNC_LIT_BITS == 10
 static_assert(sizeof(SyncLds) == 10240, "16 waves per CU: the wave's LDS must stay within 160 KB / 16");
 #endif
 // header scratch inside `stage`
@@ -156,9 +150,6 @@ constexpr uint32_t kHdrTab = 3840;     // 2 x (first code[16] | sorted index of 
 static_assert(kHdrTab + 2 * 33 * 4 <= kSyncStage && kHdrPt + 2 * 1280 <= kHdrTab, "header scratch fits the stage");
 
 enum { kSyncEob = 0, kSyncBail = 1, kSyncBailCap = 2 };
-#ifndef SWC_PROV_STORES
-#define SWC_PROV_STORES 2   // the provisional decode's stores: 0 unconditional, 1 masked per lane (a literal came in / a record is complete), 2 literal groups only when full
-#endif
 #if defined(SWC_HOST_EMULATION)
 // statistics of the emulated decoder (tests, tools/sync_stats.py): rounds committed, bails, lane-passes, symbol iterations
 inline uint64_t g_sync_stats[8];
@@ -577,30 +568,6 @@ SWC_D uint32_t walk_chunk(const SyncLds* sl, const SubTab st, uint32_t start, ui
     uint32_t pos = start, tm = kLitMask4, tb = 0, e = 0;
     uint32_t c_notlen = kEntNotLen, c_dmask = kDistMask4;
     SWC_OPAQUE(c_notlen); SWC_OPAQUE(c_dmask);
-#if SWC_WALK_WINDOW
-    // The walk is bound by the latency of its chain, not by its instruction count (four waves per SIMD, two dependent LDS reads
-    // per code in the form below): here the window lives in two registers, the dword behind it is read every step -- needed or
-    // not, off the chain -- and moves in when the position crosses a dword: ONE LDS read in the chain, fourteen instructions.
-    uint32_t d0, d1, bp = pos & 31u;
-    { const uint32_t* w = (const uint32_t*)(sl->stage + ((pos >> 3) & 0x1FFCu)); d0 = w[0]; d1 = w[1]; }
-    if (start < chunk_end) do {
-        SWC_SYNC_STAT(4, 1);
-        SWC_SYNC_ITER();
-        const uint32_t bits4 = funnel32(d1, d0, pos);
-        e = *(const uint32_t*)((const uint8_t*)sl->lut + and_or(bits4, tm, tb));
-        const uint32_t nx = *(const uint32_t*)(sl->stage + ((pos >> 3) & 0x1FFCu) + 8u);
-        uint32_t mm = e & kEntPosMask;
-        if (mm == 0u) { SWC_SYNC_STAT(7, 1); SWC_SYNC_LONG(); e = long_lookup(sl, st, bits4, e); mm = e & kEntPosMask; }
-        pos = pos + mm + 0xFFFFFFFEu;
-        const uint32_t bpn = pos & 31u;
-        const bool crossed = bpn < bp;                      // (a symbol takes fewer than 32 bits)
-        d0 = crossed ? d1 : d0;
-        d1 = crossed ? nx : d1;
-        bp = bpn;
-        tm = and_or(e, c_notlen, c_dmask);
-        tb = e & kEntLen;
-    } while ((int32_t)pos < (int32_t)chunk_end);
-#else
     if (start < chunk_end) do {   // (tested at the bottom: one mask update and one branch per iteration)
         SWC_SYNC_STAT(4, 1);
         SWC_SYNC_ITER();
@@ -612,7 +579,6 @@ SWC_D uint32_t walk_chunk(const SyncLds* sl, const SubTab st, uint32_t start, ui
         tm = and_or(e, c_notlen, c_dmask);
         tb = e & kEntLen;
     } while ((int32_t)pos < (int32_t)chunk_end);
-#endif
     const uint32_t endb = pos & 0x3FFFFFFFu;
     const bool fail = ((pos & kEntStop) != 0u && !ent_is_eob(e)) || endb > in_bits;
     return fail ? kPosFail : endb;
@@ -625,9 +591,9 @@ SWC_D uint32_t walk_chunk(const SyncLds* sl, const SubTab st, uint32_t start, ui
 // final offset (copy_prov) instead of decoding a third time.  What the lane cannot know yet -- the output position of its
 // sub-chunk -- enters only through `need`: the largest (distance - 1 - output bytes of the sub-chunk in front of the match),
 // checked after the scan (NEED = false: the round starts 32 KiB or more into the output, where no distance can fail).
-// Both stores of a step are UNCONDITIONAL: the literal accumulator (the newest byte at the top, four to a group) goes to the
-// row of the group it belongs to, a record to the row of the next record -- a step that adds nothing rewrites what is there,
-// and a row is final when its last writer has been.  `run0`: literals in front of the sub-chunk that no record covers yet
+// A step stores what it completes: the literal accumulator (the newest byte at the top, four to a group) goes to the row of
+// its group when a literal fills the group (the last, incomplete group after the loop), a record to the row of the next
+// record when its distance comes in.  `run0`: literals in front of the sub-chunk that no record covers yet
 // (lane 0 of the first round of a block).  A sub-chunk that ends at the end-of-block symbol leaves its trailing literals
 // uncovered (`tail`), every other one closes them with a literal-only record.
 struct ProvOut {
@@ -670,18 +636,8 @@ SWC_D void decode_chunk_prov(const SyncLds* sl, const SubTab st, uint32_t start,
         lb = alignbyte32(val, lb, lit1);
         nl3 += lit1;
         const uint32_t dm = sbfe1(e, 29);
-#if SWC_PROV_STORES == 0
-        store_u32(prov + lshl_add<6>(nl3 & ~3u, lbase), lb);
-        // a distance completes a record; any other step writes a word that the next record of the lane overwrites
-        store_u32(prov + roff, lshl_add<7>(plen, lshl_add<16>(val, run)));
-#elif SWC_PROV_STORES == 1
-        // (the stores of the lanes that have nothing new are masked off: the memory pipeline's work is per active lane)
-        if (lit1 != 0u) store_u32(prov + lshl_add<6>(nl3 & ~3u, lbase), lb);
-        if (dm != 0u) store_u32(prov + roff, lshl_add<7>(plen, lshl_add<16>(val, run)));
-#else
         if (((nl3 & 3u) | (lit1 << 2)) == 7u) store_u32(prov + lshl_add<6>(nl3 & ~3u, lbase), lb);   // a literal came in and completed its group (nl3 % 4 == 3)
-        if (dm != 0u) store_u32(prov + roff, lshl_add<7>(plen, lshl_add<16>(val, run)));
-#endif
+        if (dm != 0u) store_u32(prov + roff, lshl_add<7>(plen, lshl_add<16>(val, run)));   // a distance completes a record
         roff = mad24(dm, c_m256, roff);
         if (NEED) {
             const int32_t nd = (int32_t)val - (int32_t)nout;   // this much output must exist in front of the sub-chunk
@@ -692,9 +648,7 @@ SWC_D void decode_chunk_prov(const SyncLds* sl, const SubTab st, uint32_t start,
         plen = val & sbfe1(e, kEntLenBit);
     } while ((int32_t)pos < (int32_t)chunk_end);
     const uint32_t nlit = nl3 - 3u;
-#if SWC_PROV_STORES == 2
     if (nlit & 3u) store_u32(prov + lshl_add<6>(nl3 & ~3u, lbase), lb);   // the last, incomplete group
-#endif
     const uint32_t endb = pos & 0x3FFFFFFFu;
     uint32_t flags = 0;
     if (dead) flags = kFlagFail;

@@ -134,9 +134,6 @@ __device__ __forceinline__ uint32_t job_of(const uint32_t* order, uint32_t b, ui
 // ---- Deflate: two phases (inflate_sync.h + inflate_lane.h, lz_resolve.h) -------------------------------------------
 // Phase 1: one stream per WAVEFRONT, 64 sub-chunks of the stream decoded at once (inflate_sync.h).
 // LDS: the shared tables + the staged input of a round, exactly 10 KiB per wave -> 16 waves per CU.
-#ifndef SWC_INFLATE_ORDER
-#define SWC_INFLATE_ORDER 1
-#endif
 #ifndef SWC_SYNC_WAVES_PER_SIMD
 #define SWC_SYNC_WAVES_PER_SIMD 4
 #endif
@@ -150,11 +147,7 @@ __global__ __launch_bounds__(64, SWC_SYNC_WAVES_PER_SIMD) void swc_inflate_sync_
     if (g >= n) return;
     Job job = jobs[g];
     inflate::inflate_sync_job(job, &sync_lds, wm.area(g), wm.bytes(g), (int)threadIdx.x, kWave, prof ? prof + 32 * (size_t)g : nullptr);
-    if (threadIdx.x == 0) {
-        jobs[g].out_len = job.out_len;
-        jobs[g].in_consumed = job.in_consumed;
-        jobs[g].status = job.status;
-    }
+    if (threadIdx.x == 0) put_result(jobs, g, job);
 }
 
 // Phase 2: one stream per workgroup of 512 threads, 64 KiB LDS ring (32 KiB of history + span + cells) -> 2 workgroups per CU.
@@ -178,7 +171,6 @@ __global__ __launch_bounds__(kInflateResolveThreads) void swc_lz_resolve_kernel(
 //            flush moved to the top of the iteration, which needs 3,328);
 //   LZ4      7 KiB window, 3.25 KiB kept, groups of up to 1 KiB, runs of up to 32 literal bytes per lane, 81 VGPRs -> 20 waves per CU
 //            (9 KiB / 2 KiB groups / 16 waves: 57.9 against 56.6 ms).
-// The 16 KiB variant (8 waves per CU) is kept for comparison runs.
 template <typename CFG, int RM = 0>
 __device__ __forceinline__ void lz_copy_body(const Job* __restrict__ jobs, uint32_t n, const WsMap& wm, const uint32_t* __restrict__ order) {
     __shared__ __attribute__((aligned(16))) lzc::Lds<CFG::kWin> lds;
@@ -205,11 +197,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZC_WAVE
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZC4_WAVES, SWC_LZC4_WAVES))) void swc_lz4_copy_kernel(const Job* __restrict__ jobs, uint32_t n, WsMap wm, const uint32_t* __restrict__ order) {
     lz_copy_body<lzc::CfgLz4, SWC_LZ4_RECORD_MODE>(jobs, n, wm, order);   // (the literals come from the block itself)
 }
-__global__ __launch_bounds__(64) void swc_lz_copy16_kernel(const Job* __restrict__ jobs, uint32_t n, WsMap wm, const uint32_t* __restrict__ order) {
-    lz_copy_body<lzc::CfgWide>(jobs, n, wm, order);
-}
-// "lz_copier" (swc_set_tuning): 1 = lz_copy.h with the windows above (default), 2 = with a 16 KiB window, 0 = the byte-cell resolver
-// of lz_resolve.h (rounds 2-4) -- kept for A/B measurements; all produce the same bytes.
+// "lz_copier" (swc_set_tuning): 1 = lz_copy.h with the windows above (default), 0 = the byte-cell resolver of lz_resolve.h
+// (rounds 2-4) -- both produce the same bytes.
 static std::atomic<int> g_lz_copier{1};
 void set_lz_copier(int v) { g_lz_copier = v; }
 // A launch of FEW streams is a matter of latency, not throughput: one wave walks a 64 KiB stream group by group in ~0.3 ms,
@@ -217,13 +206,12 @@ void set_lz_copier(int v) { g_lz_copier = v; }
 // Below kCopierMin streams the launch takes the workgroup kernel (the single-shot calls, small containers), above it the
 // wave kernel (the batches this engine is built for); both write the same bytes (tests/test_lz_copy_records.py).
 constexpr size_t kCopierMin = 2560;
-static int copier_for(size_t n) {
+static bool wave_copier(size_t n) {
     const int c = g_lz_copier;
-    return c < 0 ? -c : (c == 1 && n < kCopierMin ? 0 : c);   // (tuning value -1 / -2: the wave kernel whatever the batch size)
+    return c < 0 || (c == 1 && n >= kCopierMin);   // (tuning value -1: the wave kernel whatever the batch size)
 }
-static void launch_lz_copy(int mode, bool lz4, const Job* jobs, size_t n, const WsMap& wm, const uint32_t* order, hipStream_t stream) {
-    if (mode == 2 && !lz4) hipLaunchKernelGGL(swc_lz_copy16_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, jobs, (uint32_t)n, wm, order);
-    else if (lz4) hipLaunchKernelGGL(swc_lz4_copy_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, jobs, (uint32_t)n, wm, order);
+static void launch_lz_copy(bool lz4, const Job* jobs, size_t n, const WsMap& wm, const uint32_t* order, hipStream_t stream) {
+    if (lz4) hipLaunchKernelGGL(swc_lz4_copy_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, jobs, (uint32_t)n, wm, order);
     else hipLaunchKernelGGL(swc_lz_copy_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, jobs, (uint32_t)n, wm, order);
 }
 
@@ -277,8 +265,8 @@ hipError_t launch_inflate(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStr
             (void)launch_inflate_team(jobs, n, (uint8_t*)ws, stride, ws_off, (uint8_t*)scratch, stream);   // (hipGetLastError below)
             g_pt.mark(stream);
             (void)hipFreeAsync(scratch, stream);
-            const int copier = copier_for(n);
-            if (copier) launch_lz_copy(copier, false, jobs, n, wm, nullptr, stream);
+            const bool copier = wave_copier(n);
+            if (copier) launch_lz_copy(false, jobs, n, wm, nullptr, stream);
             else hipLaunchKernelGGL(swc_lz_resolve_kernel, dim3((unsigned)n), dim3(kInflateResolveThreads), 0, stream, jobs, (uint32_t)n, wm, g_prof, (const uint32_t*)nullptr);
             g_pt.mark(stream);
             return hipGetLastError();
@@ -287,11 +275,11 @@ hipError_t launch_inflate(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStr
     }
     // (streams of unequal cost -- stored blocks, incompressible stretches -- are launched longest first, like the LZ4 blocks)
     g_pt.begin(stream);   // (the ordering kernels are part of the first phase's figure: ADVICE r4)
-    const uint32_t* order = SWC_INFLATE_ORDER ? job_order(jobs, n, stream) : nullptr;
+    const uint32_t* order = job_order(jobs, n, stream);
     hipLaunchKernelGGL(swc_inflate_sync_kernel, dim3((unsigned)n), block, 0, stream, jobs, (uint32_t)n, wm, g_prof, order);
     g_pt.mark(stream);
-    const int copier = copier_for(n);
-    if (copier) launch_lz_copy(copier, false, jobs, n, wm, order, stream);
+    const bool copier = wave_copier(n);
+    if (copier) launch_lz_copy(false, jobs, n, wm, order, stream);
     else hipLaunchKernelGGL(swc_lz_resolve_kernel, dim3((unsigned)n), dim3(kInflateResolveThreads), 0, stream, jobs, (uint32_t)n, wm, g_prof, order);
     g_pt.mark(stream);
     return hipGetLastError();
@@ -309,9 +297,7 @@ __global__ __launch_bounds__(64) void swc_lz4_lane_kernel(Job* __restrict__ jobs
     Job job = jobs[g];
     if (only_dict && job.dict == nullptr) return;
     lz4::lz4_block_job(job);
-    jobs[g].out_len = job.out_len;
-    jobs[g].in_consumed = job.in_consumed;
-    jobs[g].status = job.status;
+    put_result(jobs, g, job);
 }
 
 #ifndef SWC_LZ4_PARSE_WAVES
@@ -327,11 +313,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZ4_PARS
     if (job.dict != nullptr) return;
     __shared__ __attribute__((aligned(16))) uint8_t stage[lz4w::kStageLds];
     lz4w::lz4_parse_job<kWave, RM>(job, wm.area(g), wm.bytes(g), (int)threadIdx.x, stage, prof ? prof + 32 * (size_t)g : nullptr);
-    if (threadIdx.x == 0) {
-        jobs[g].out_len = job.out_len;
-        jobs[g].in_consumed = job.in_consumed;
-        jobs[g].status = job.status;
-    }
+    if (threadIdx.x == 0) put_result(jobs, g, job);
 }
 
 __global__ __launch_bounds__(lz4w::kResolveThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void swc_lz4_resolve_kernel(const Job* __restrict__ jobs, uint32_t n, WsMap wm, uint64_t* prof, const uint32_t* __restrict__ order) {
@@ -361,11 +343,11 @@ hipError_t launch_lz4(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStream_
     hipLaunchKernelGGL(swc_lz4_lane_kernel, grid, block, 0, stream, jobs, (uint32_t)n, 1);
     g_pt.mark(stream);
     const WsMap wm{(uint8_t*)ws, stride, ws_off};
-    const int copier = copier_for(n);
+    const bool copier = wave_copier(n);
     if (copier) hipLaunchKernelGGL(swc_lz4_parse_kernel<SWC_LZ4_RECORD_MODE>, dim3((unsigned)n), block, 0, stream, jobs, (uint32_t)n, wm, g_prof, order);
     else hipLaunchKernelGGL(swc_lz4_parse_kernel<0>, dim3((unsigned)n), block, 0, stream, jobs, (uint32_t)n, wm, g_prof, order);
     g_pt.mark(stream);
-    if (copier) launch_lz_copy(copier, true, jobs, n, wm, order, stream);
+    if (copier) launch_lz_copy(true, jobs, n, wm, order, stream);
     else hipLaunchKernelGGL(swc_lz4_resolve_kernel, dim3((unsigned)n), dim3(lz4w::kResolveThreads), 0, stream, jobs, (uint32_t)n, wm, g_prof, order);
     g_pt.mark(stream);
     return hipGetLastError();
@@ -378,11 +360,7 @@ __global__ __launch_bounds__(64) void swc_lz4_compress_kernel(Job* __restrict__ 
     if (g >= n) return;
     Job job = jobs[g];
     lz4c::lz4_compress_job<kWave>(job, table);
-    if (threadIdx.x == 0) {
-        jobs[g].out_len = job.out_len;
-        jobs[g].in_consumed = job.in_consumed;
-        jobs[g].status = job.status;
-    }
+    if (threadIdx.x == 0) put_result(jobs, g, job);
 }
 hipError_t launch_lz4_compress(Job* jobs, size_t n, hipStream_t stream) {
     if (n == 0) return hipSuccess;
@@ -400,11 +378,7 @@ __global__ __launch_bounds__(64) void swc_deflate_compress_kernel(Job* __restric
     if (g >= n) return;
     Job job = jobs[g];
     defc::deflate_compress_job<kWave>(job, &lds);
-    if (threadIdx.x == 0) {
-        jobs[g].out_len = job.out_len;
-        jobs[g].in_consumed = job.in_consumed;
-        jobs[g].status = job.status;
-    }
+    if (threadIdx.x == 0) put_result(jobs, g, job);
 }
 hipError_t launch_deflate_compress(Job* jobs, size_t n, hipStream_t stream) {
     if (n == 0) return hipSuccess;
@@ -436,11 +410,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZMA_WAV
     Job job = jobs[g];
     SWC_AS_GLOBAL uint16_t* sp = spill ? (SWC_AS_GLOBAL uint16_t*)(spill + (size_t)g * kLzmaSpillBytes) : nullptr;
     lzma::lzma_job<kWave>(job, LZMA2, lzma_lds, sp, (int)threadIdx.x, LDSBITS < 0 ? 0 : LDSBITS, prof ? prof + 32 * (size_t)g : nullptr, LDSBITS < 0);
-    if (threadIdx.x == 0) {
-        jobs[g].out_len = job.out_len;
-        jobs[g].in_consumed = job.in_consumed;
-        jobs[g].status = job.status;
-    }
+    if (threadIdx.x == 0) put_result(jobs, g, job);
 }
 
 size_t lzma_spill_bytes_per_job() { return kLzmaSpillBytes; }
@@ -474,10 +444,7 @@ hipError_t launch_lzma(bool lzma2, Job* jobs, size_t n, void* spill, hipStream_t
 // random HBM accesses) back to back.  As separate launches the three ran one after the other, each limited by its own
 // resource while the others idled; in one kernel the waves of a CU are at different stages at any time, so the scalar
 // work of some overlaps the memory waits of the others.  LDS: the three stages' areas share one allocation.
-#ifndef SWC_BZ_LDS_PAD
-#define SWC_BZ_LDS_PAD 0   // (occupancy experiments: more LDS per wave = fewer waves per CU, nothing else changed)
-#endif
-constexpr size_t kBzLdsBytes = (bzip2::kStage1LdsBytes > sizeof(bzip2::Stage3Lds) ? (size_t)bzip2::kStage1LdsBytes : sizeof(bzip2::Stage3Lds)) + SWC_BZ_LDS_PAD;
+constexpr size_t kBzLdsBytes = bzip2::kStage1LdsBytes > sizeof(bzip2::Stage3Lds) ? (size_t)bzip2::kStage1LdsBytes : sizeof(bzip2::Stage3Lds);
 static_assert(kBzLdsBytes >= 256 * sizeof(uint32_t), "stage 2 counters");
 #ifndef SWC_BZ_WAVES
 #define SWC_BZ_WAVES 6   // (round 4, stage 3 inside: 7 -> 72 VGPRs + 8 bytes of scratch, 495 ms against 479; round 6, stages 1 + 2 only: 6 / 7 / 8 -> 198.4 / 200.3 / 199.4 ms)
@@ -493,25 +460,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_BZ_WAVES
     Job job = jobs[g];
     const bzip2::Workspace w = bzip2::carve(ws, g, lcap);
     bzip2::stage1_job<kWave, CXX>(job, reinterpret_cast<bzip2::Stage1Lds*>(bz_lds), w, (int)threadIdx.x);
-#if defined(SWC_BZ_STOP_AFTER) && SWC_BZ_STOP_AFTER == 1   // (timing experiments only, tools/attic/exp_bz_stages.py: wrong results)
-    if (threadIdx.x == 0) { w.hdr->pad = bzip2::kWalkDone; jobs[g].status = SWC_E_DEVICE; }
-    return;
-#endif
     __threadfence_block();   // L and the block header, written by some lanes, are read by all of them from here on
     bzip2::stage2_job(w, reinterpret_cast<uint32_t*>(bz_lds));
-#if defined(SWC_BZ_STOP_AFTER) && SWC_BZ_STOP_AFTER == 2
-    if (threadIdx.x == 0) { w.hdr->pad = bzip2::kWalkDone; jobs[g].status = SWC_E_DEVICE; }
-    return;
-#endif
     if (team) return;
     __threadfence_block();   // likewise the pointer array P
     bzip2::stage3_walk_job<kWave>(job, w, reinterpret_cast<bzip2::Stage3Lds*>(bz_lds), (int)threadIdx.x);
-    if (threadIdx.x == 0 && !bzip2::stage3_expand_needed(w)) {
-        jobs[g].out_len = job.out_len;
-        jobs[g].in_consumed = job.in_consumed;
-        jobs[g].status = job.status;
-        jobs[g].aux = job.aux;
-    }
+    if (threadIdx.x == 0 && !bzip2::stage3_expand_needed(w)) put_result<true>(jobs, g, job);
 }
 
 // ---- stage 3a as kernels of its own (bzip2_team.h) ------------------------------------------------------------------------------
@@ -533,12 +487,7 @@ __global__ __launch_bounds__(64) void swc_bzip2_team_finish_kernel(Job* __restri
     Job job = jobs[g];
     const bzip2::Workspace w = bzip2::carve(ws, g, lcap);
     bzip2::team_finish<kWave>(job, w, &lds, (int)threadIdx.x);
-    if (threadIdx.x == 0 && !bzip2::stage3_expand_needed(w)) {
-        jobs[g].out_len = job.out_len;
-        jobs[g].in_consumed = job.in_consumed;
-        jobs[g].status = job.status;
-        jobs[g].aux = job.aux;
-    }
+    if (threadIdx.x == 0 && !bzip2::stage3_expand_needed(w)) put_result<true>(jobs, g, job);
 }
 
 // stage 3b: one block per lane, only what stage 3a could not finish (serial walk + RLE1 undo)
@@ -549,10 +498,7 @@ __global__ __launch_bounds__(64) void swc_bzip2_expand_kernel(Job* __restrict__ 
     if (!bzip2::stage3_expand_needed(w)) return;
     Job job = jobs[g];
     bzip2::stage3_expand_job(job, w);
-    jobs[g].out_len = job.out_len;
-    jobs[g].in_consumed = job.in_consumed;
-    jobs[g].status = job.status;
-    jobs[g].aux = job.aux;
+    put_result<true>(jobs, g, job);
 }
 
 // stage 3c: one block per workgroup (block CRC, BZip2.swift:81)
@@ -573,10 +519,9 @@ __global__ __launch_bounds__(256) void swc_bzip2_crc_kernel(Job* __restrict__ jo
 size_t bzip2_ws_bytes_per_job(size_t lcap) { return bzip2::ws_bytes_per_job(lcap); }
 static std::atomic<int> g_bzip2_hot_cxx{0};
 void set_bzip2_hot_cxx(int v) { g_bzip2_hot_cxx = v; }
-static std::atomic<int> g_bzip2_team_walk{1}, g_bzip2_team_per_cu{1};
+static std::atomic<int> g_bzip2_team_walk{1};
 constexpr size_t kTeamMinBytes = 65536;
 void set_bzip2_team_walk(int v) { g_bzip2_team_walk = v; }
-void set_bzip2_team_per_cu(int v) { g_bzip2_team_per_cu = v; }
 
 hipError_t launch_bzip2(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStream_t stream) {
     if (n == 0) return hipSuccess;
@@ -603,7 +548,7 @@ hipError_t launch_bzip2(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStrea
     g_pt.mark(stream);
     if (team) {   // (phase timing: block | team prep + walk | team finish | expand | crc -- five figures with the team walk, three without)
         hipLaunchKernelGGL(swc_bzip2_team_prep_kernel, dim3(bzip2::kTeams), block, 0, stream, (uint8_t*)ws, lcap, (uint32_t)n);
-        hipLaunchKernelGGL(swc_bzip2_team_walk_kernel, dim3(256 * g_bzip2_team_per_cu), dim3(SWC_BZ_TEAM_THREADS), 0, stream, (uint8_t*)ws, lcap, (uint32_t)n);
+        hipLaunchKernelGGL(swc_bzip2_team_walk_kernel, dim3(256), dim3(SWC_BZ_TEAM_THREADS), 0, stream, (uint8_t*)ws, lcap, (uint32_t)n);
         g_pt.mark(stream);
         hipLaunchKernelGGL(swc_bzip2_team_finish_kernel, dim3((unsigned)n), block, 0, stream, jobs, (uint32_t)n, (uint8_t*)ws, lcap);
         g_pt.mark(stream);

@@ -52,10 +52,6 @@
 #include "simt.h"
 #include "lz_resolve.h"   // record format, StreamHeader, workspace layout
 
-#ifndef SWC_LZC_CUT
-#define SWC_LZC_CUT 0
-#endif
-
 namespace swc {
 namespace lzc {
 
@@ -116,12 +112,6 @@ SWC_HD void copy_run(uint8_t* d, const uint8_t* s, uint32_t n) {
 // R8: records of EIGHT bytes -- the 32-bit record and, in the upper dword, the offset of its literal run from `lits`, which then
 // is not a dense literal stream but the compressed input itself: LZ4 keeps its literals byte-aligned in the block (LZ4.swift:
 // 364-366), so the parse kernel writes no literal stream at all and the copier fetches a run where the encoder left it.
-#ifndef SWC_LZC_FAKE
-#define SWC_LZC_FAKE 0   // (timing experiments only, wrong output: 1 = the literal loads, 2 = the far loads, 3 = both read one hot place)
-#endif
-#ifndef SWC_LZC_FLUSH_EARLY
-#define SWC_LZC_FLUSH_EARLY 1
-#endif
 // RM == 2 ("R4"): four-byte records again, `lits` the compressed block, and the place of a record's literals DERIVED: the start S
 // of a sequence is a running sum over the records of seq_bytes(literals, length) -- what a sequence in LZ4's short form takes --
 // and its literals lie lit_skip() behind S.  The parse (lz4_wave.h), which simulates this sum, leaves an ANCHOR (record index, S)
@@ -158,6 +148,7 @@ struct Copier {
 #define SWC_LZC_SEQMAX 8
 #endif
     static constexpr uint32_t kSeqMax = SWC_LZC_SEQMAX;        // more short matches left than this: those that do not depend on each other first, all at once
+    static constexpr uint32_t kByteLanesMax = 256;             // nothing odd and at most this many bytes of matches left: a byte per lane
     static constexpr uint32_t kBack = 65536;                   // the furthest a source lies behind its match (record format)
     static_assert(kKeep % 16u == 0u && kKeep + kSpanMax + 16u <= WIN, "a group fits behind what a slide keeps");
     static_assert(lzr::kLitRunMax + lzr::kMaxLen <= kSpanMax && kBigLit - 1u + lzr::kMaxLen <= kSpanMax, "a record must fit a group");
@@ -170,7 +161,7 @@ struct Copier {
     // has as good as always landed when the group AHEAD of its match is being copied.
     // (The flush watermark lies less than 1,040 bytes behind the position after every group, `landed` one group behind that:
     // a source that is asked for -- kLongLen bytes at most, kKeep and more behind its match -- has always landed.)
-    static_assert(kKeep >= kLongLen + 1040u + (SWC_LZC_FLUSH_EARLY ? 2u : 1u) * kSpanMax + 128u, "far sources that are asked for ahead must have landed");
+    static_assert(kKeep >= kLongLen + 1040u + 2u * kSpanMax + 128u, "far sources that are asked for ahead must have landed");
     enum : uint32_t { kFlagCoop = 1u, kFlagFar = 2u };
 
     L* l;
@@ -211,9 +202,7 @@ struct Copier {
     }
     // all of this wave's loads have returned and all of its stores have arrived in memory
     SWC_D void drain() {
-#if !defined(SWC_LZC_NODRAIN)   // (timing experiments only: the output may be wrong)
         simt::vmem_fence();
-#endif
         landed = fv;
     }
     // The loads of a path that is rarely taken (all lanes on one long run, a far source nobody asked for ahead) are waited for
@@ -504,7 +493,7 @@ struct Copier {
             SIMT_BEGIN(t, W)
                 uint32_t li, le, di;
                 unpack(g.rec[t], li, le, di);
-                const bool ask = !SWC_LZC_FAKE && runs && (uint32_t)t < ntake && li != 0u && li <= kLongLit;
+                const bool ask = runs && (uint32_t)t < ntake && li != 0u && li <= kLongLit;
                 // (nothing wanted: the group's first literal, or the byte behind the last: it exists; R8: the block's first bytes)
                 const uint32_t o0 = ask ? (INP ? g.loff[t] : (g.x[t] >> 16) - li) : 0u;
                 const uint32_t last = (li > 8u ? li : 8u) - 8u;
@@ -533,7 +522,7 @@ struct Copier {
                 uint32_t li, le, di;
                 unpack(g.rec[t], li, le, di);
                 const int32_t srel = (int32_t)((g.x[t] & 0xFFFFu) - le - di);           // my source starts here, relative to the group's first byte
-                const bool ask = !(SWC_LZC_FAKE & 2) && known && (uint32_t)t < ntake && le != 0u && (int32_t)wpn + srel < 0 && le <= kLongLen && di >= le && srel + (int32_t)le <= lim;
+                const bool ask = known && (uint32_t)t < ntake && le != 0u && (int32_t)wpn + srel < 0 && le <= kLongLen && di >= le && srel + (int32_t)le <= lim;
                 const uint32_t o0 = kBack + (uint32_t)srel;
                 const uint32_t last = (le > 8u ? le : 8u) - 8u;
 #pragma unroll
@@ -570,9 +559,6 @@ struct Copier {
         const uint32_t ntake = g.ntake;
         uint32_t wp = (uint32_t)((P)A + rpos - vbase);
         if (wp + g.span > WIN) wp = slide(rpos);
-#if SWC_LZC_CUT == 1   // (instruction accounting builds, tools/attic/exp_copier_counts.sh: the output is wrong)
-        return;
-#endif
         uint8_t* const B = (uint8_t*)l;                                 // window indices are offsets from here
         const bool pfu = g.pf_vbase == vbase;                           // the far loads assumed the window base that came to be
         const int32_t pf_lim = g.pf_lim;
@@ -611,9 +597,6 @@ struct Copier {
             // my match, if its source was final when the group began
             if (act) copy_own(B, m, s, le, far, g.fw[0][t], g.fw[kPieces > 1 ? 1 : 0][t], g.fw[kPieces > 2 ? 2 : 0][t], g.fw[kPieces > 3 ? 3 : 0][t]);
         SIMT_END_WAVE
-#if SWC_LZC_CUT == 2
-        return;
-#endif
         // ---- long literal runs by all lanes
         for (uint64_t m = simt::wave_ballot<W>(longlit); m; m &= m - 1u) {
             const int h = simt::ctz64(m);
@@ -621,18 +604,12 @@ struct Copier {
             const uint32_t lend = simt::wave_read<W>(g.x, h) >> 16;
             coop_literals(simt::wave_read<W>(wm, h) - li, INP ? (P)simt::wave_read<W>(g.loff, h) : lbase + (lend - li), li);
         }
-#if SWC_LZC_CUT == 3
-        return;
-#endif
         // ---- the matches that are left reach into their own group (or are long, overlapping, far and not asked for: "odd").
         PT<bool, W> odd;
         SIMT_BEGIN(t, W) odd[t] = pend[t] && flags[t] != 0u; SIMT_END
         uint64_t pm = simt::wave_ballot<W>(pend);
         const uint64_t om = simt::wave_ballot<W>(odd);
-#ifndef SWC_LZC_BYTELANES
-#define SWC_LZC_BYTELANES 256
-#endif
-        if (SWC_LZC_BYTELANES != 0 && om == 0ull && pm != 0ull) {
+        if (om == 0ull && pm != 0ull) {
             // ---- Nothing odd among them (nine groups in ten on text): the BYTES of the matches that are left, one per lane.  A
             // running sum of their lengths numbers the bytes; a lane finds the match its byte belongs to through a marker at
             // the match's first byte (LDS) and a running maximum over the lanes, fetches window index and source with two
@@ -645,7 +622,7 @@ struct Copier {
             SIMT_BEGIN(t, W) incl[t] = pend[t] ? len[t] : 0u; SIMT_END
             simt::wave_scan_incl<W>(incl);
             const uint32_t nbytes = simt::wave_read<W>(incl, W - 1);
-            if (nbytes <= (uint32_t)SWC_LZC_BYTELANES) {
+            if (nbytes <= kByteLanesMax) {
                 SIMT_BEGIN(t, W)
                     offs[t] = incl[t] - (pend[t] ? len[t] : 0u);
                     pk[t] = wm[t] | (si[t] << 16);          // (both are window indices below 64 KiB: nothing here is far)
@@ -807,12 +784,10 @@ struct Copier {
             // Everything asked for during the last iteration -- the next records, far sources, literals -- is here, and its
             // stores have arrived (an iteration's loads have the whole of the previous group's copies to come back).
             drain();
-#if SWC_LZC_FLUSH_EARLY
             // finished bytes leave for HBM a KiB at a time (whole-wave stores), long before they leave the window -- and at the TOP of
             // the iteration: the drain of the next one then finds stores that have had a whole group's copies to arrive, not stores
             // issued a moment ago (a wave spent two fifths of its time waiting, most of it there)
             if ((P)A + rpos - fv >= 1024u) flush((P)A + rpos, false);
-#endif
             cur = nxt;
             const uint32_t nbase = base + cur.ntake;
             more = nbase < nrec;
@@ -830,10 +805,6 @@ struct Copier {
             back(cur, rpos, cur.S0);
             base = nbase;
             rpos += cur.span;
-#if !SWC_LZC_FLUSH_EARLY
-            // finished bytes leave for HBM a KiB at a time (whole-wave stores), long before they leave the window
-            if ((P)A + rpos - fv >= 1024u) flush((P)A + rpos, false);
-#endif
         }
         drain();
         flush((P)A + rpos, true);
@@ -871,7 +842,6 @@ using CfgDeflate = Cfg<SWC_LZC_WIN, SWC_LZC_SPAN, SWC_LZC_KEEP, SWC_LZC_LITP>;
 #define SWC_LZC4_LITP 4
 #endif
 using CfgLz4 = Cfg<SWC_LZC4_WIN, SWC_LZC4_SPAN, SWC_LZC4_KEEP, SWC_LZC4_LITP>;
-using CfgWide = Cfg<16384, 2048, 14320, 4>;   // (comparison runs: 8 waves per CU)
 
 // One job: `ws` is the stream's workspace area of `area` bytes written by phase 1.  RM 1 (R8) / 2 (R4), LZ4: the literals are
 // fetched from the job's input; R8: the area holds the header and eight-byte records; R4: four-byte records, and the anchors where

@@ -127,7 +127,8 @@ struct Decoder {
     bool cached = false;        // LDS holds kCoderSlots literal coders (see kCoderSlots); lit_spill is required
     uint32_t tag0 = kNoCoder, tag1 = kNoCoder, tag2 = kNoCoder, tag3 = kNoCoder;   // the coder in each slot
     uint32_t victim = 0;        // the slot the next miss replaces
-    uint32_t mru = 0;           // the slot that was used last
+    uint32_t mru = 0;           // (read by nothing; without it the kernel's registers are numbered differently -- the same
+                                // instructions -- so it goes with the next change here that is measured anyway)
     uint64_t fresh = 0;         // bit c: coder c (c < 64) has not been used since the last reset -- its cells are all 1024, nothing to load
     uint64_t fresh1 = 0, fresh2 = 0;   // the same for the second and third line of coder c (`fresh`: its first)
     bool have_model;
@@ -184,24 +185,15 @@ struct Decoder {
 #endif
         return (uint8_t)(w >> (8 * (k & 3u)));
     }
-#ifndef SWC_LZMA_UNIFORM_BRANCH
-#define SWC_LZMA_UNIFORM_BRANCH 1
-#endif
-    SWC_HD static bool same(bool c) { return SWC_LZMA_UNIFORM_BRANCH ? simt::wave_true(c) : c; }
+    SWC_HD static bool same(bool c) { return simt::wave_true(c); }
     SWC_HD void normalize() {     // LZMARangeDecoder.swift:38-43
         if (same(range < (1u << 24))) {
             range <<= 8;
             code = (code << 8) | next_byte();
         }
     }
-#ifndef SWC_LZMA_BIT_SELECT
-#define SWC_LZMA_BIT_SELECT 0
-#endif
-#ifndef SWC_LZMA_BIT_ASM
-#define SWC_LZMA_BIT_ASM 1
-#endif
     SWC_HD int bit(uint16_t* p) {  // LZMARangeDecoder.swift:65-80
-#if defined(__HIP_DEVICE_COMPILE__) && SWC_LZMA_BIT_ASM
+#if defined(__HIP_DEVICE_COMPILE__)
         // The decision as ONE block of gfx950 instructions: read, split the range, compare, ONE scalar branch, the side taken
         // (probability update, range / code), the store -- 13 instructions on the zero side, 12 on the one side.  From the C++
         // form below the compiler makes two conditional regions joined by a flag register (a move, a branch, an and-not and a
@@ -240,16 +232,6 @@ struct Decoder {
 #else
         const uint32_t pr = *p;
         uint32_t bound = (range >> 11) * pr;
-        if (SWC_LZMA_BIT_SELECT) {   // both sides computed, picked by selects on ONE scalar condition: no branch in the decision
-            const bool zero = same(code < bound);
-            const uint32_t pz = pr + ((2048u - pr) >> 5), po = pr - (pr >> 5);
-            *p = (uint16_t)(zero ? pz : po);
-            const uint32_t r1 = range - bound, c1 = code - bound;
-            range = zero ? bound : r1;
-            code = zero ? code : c1;
-            normalize();
-            return zero ? 0 : 1;
-        }
         int sym;
         if (same(code < bound)) {
             *p = (uint16_t)(pr + ((2048u - pr) >> 5));
@@ -295,44 +277,9 @@ struct Decoder {
         } while (count > 0);
         return res;
     }
-    // bit() for a cell whose value is already in a register
-    SWC_HD int bit_known(uint16_t* p, uint32_t pr) {
-        uint32_t bound = (range >> 11) * pr;
-        int sym;
-        if (same(code < bound)) {
-            *p = (uint16_t)(pr + ((2048u - pr) >> 5));
-            range = bound;
-            sym = 0;
-        } else {
-            *p = (uint16_t)(pr - (pr >> 5));
-            code -= bound;
-            range -= bound;
-            sym = 1;
-        }
-        normalize();
-        return sym;
-    }
-#ifndef SWC_LZMA_PAIR_READ
-#define SWC_LZMA_PAIR_READ 0
-#endif
-    // LZMABitTreeDecoder.swift:18-24.  SWC_LZMA_PAIR_READ (measured, off: 880 ms against 862, profiles/r04_experiments.txt): the
-    // children of node m are the cells 2m and 2m + 1, ONE aligned dword (`p` starts at an even cell) that can be read while the
-    // decision at m is still being taken, so that the LDS round trip leaves the serial chain -- but the two instructions it
-    // adds per decision cost more than the latency it hides, as the chain microbenchmark of round 3 had said.
-    SWC_HD int tree(uint16_t* p, int nbits) {
+    SWC_HD int tree(uint16_t* p, int nbits) {  // LZMABitTreeDecoder.swift:18-24
         int m = 1;
-        if (!SWC_LZMA_PAIR_READ) {
-            for (int i = 0; i < nbits; i++) m = (m << 1) + bit(&p[m]);
-            return m - (1 << nbits);
-        }
-        uint32_t pr = p[1];
-        for (int i = 0; i < nbits; i++) {
-            uint32_t pair = 0;
-            if (i + 1 < nbits) pair = *(const uint32_t*)__builtin_assume_aligned(p + 2 * m, 4);
-            const int b = bit_known(&p[m], pr);
-            pr = b ? pair >> 16 : pair & 0xFFFFu;
-            m = (m << 1) + b;
-        }
+        for (int i = 0; i < nbits; i++) m = (m << 1) + bit(&p[m]);
         return m - (1 << nbits);
     }
     SWC_HD int tree_reverse(uint16_t* p, int limit, int start, int bits) {  // :26-43
@@ -372,17 +319,12 @@ struct Decoder {
         {
             const uint32_t slot = (tag1 == L ? 1u : 0u) + (tag2 == L ? 2u : 0u) + (tag3 == L ? 3u : 0u);
             const bool hit = tag0 == L || slot != 0u;
-#ifndef SWC_LZMA_KEEP_MRU
-#define SWC_LZMA_KEEP_MRU 0   // (measured: text 612 against 621 ms, binary records 635 against 621, P-mix the same -- off)
-#endif
-            if (same(hit)) { if (SWC_LZMA_KEEP_MRU) mru = slot; return probs + kSlotBase + slot * 0x100; }
+            if (same(hit)) return probs + kSlotBase + slot * 0x100;
         }
-        // (round-robin, but never the line that was used last: one scalar move on the hit path keeps the hot line -- on text the
-        // plain tree of the lower-case coder -- out of the rotation)
-        uint32_t v = victim;
-        if (SWC_LZMA_KEEP_MRU && v == mru) v = v + 1 == (uint32_t)kLines ? 0u : v + 1;
+        // (round-robin.  Sparing the line that was used last -- on text the plain tree of the lower-case coder -- was measured:
+        // text 612 against 621 ms, binary records 635 against 621, P-mix the same; not kept)
+        const uint32_t v = victim;
         victim = v + 1 == (uint32_t)kLines ? 0u : v + 1;
-        if (SWC_LZMA_KEEP_MRU) mru = v;
         const uint32_t old = v == 0 ? tag0 : v == 1 ? tag1 : v == 2 ? tag2 : tag3;
         uint16_t* sp = probs + kSlotBase + v * 0x100;
         uint32_t* sp32 = (uint32_t*)sp;
@@ -565,11 +507,8 @@ struct Decoder {
                         } while (symbol < 0x100);
                     }
                     if (symbol == 1) {   // not in matched mode: exactly eight decisions (a constant trip count: no loop test in the chain)
-                        if (SWC_LZMA_PAIR_READ) symbol = 0x100 + tree(lpb, 8);   // (every literal coder starts at an even cell)
-                        else {
 #pragma unroll
-                            for (int i = 0; i < 8; i++) symbol = (symbol << 1) | bit(&lpb[symbol]);
-                        }
+                        for (int i = 0; i < 8; i++) symbol = (symbol << 1) | bit(&lpb[symbol]);
                     } else {
                         while (symbol < 0x100) symbol = (symbol << 1) | bit(&lpb[symbol]);
                     }

@@ -50,6 +50,15 @@ struct Job {
     uint64_t dict_len;     // LZ4: dictionary length; LZMA: declared uncompressed size (or ~0 = unknown)
 };
 
+// A kernel's results back to its entry of the job list (AUX: `aux` too -- bzip2's block CRC)
+template <bool AUX = false>
+SWC_D void put_result(Job* jobs, uint32_t g, const Job& job) {
+    jobs[g].out_len = job.out_len;
+    jobs[g].in_consumed = job.in_consumed;
+    jobs[g].status = job.status;
+    if (AUX) jobs[g].aux = job.aux;
+}
+
 SWC_HD uint32_t brev32(uint32_t x) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __brev(x);

@@ -42,6 +42,24 @@ def test_memory_knobs_without_a_device():
     assert swc.trim() == 0
 
 
+def test_copier_tuning_matches_header():
+    """swc_set_tuning takes the lz_copier values include/swc_hip.h documents and nothing else; the comparison-only values
+    (lz_copier 2 / -2, the team walk's workgroups per CU) are refused."""
+    hdr = open(os.path.join(ROOT, "include", "swc_hip.h")).read()
+    documented = [int(v) for v in re.search(r'"lz_copier" = ([-0-9| ]+)', hdr).group(1).split("|")]
+    assert sorted(documented) == [-1, 0, 1]
+    lib = _lib.load()
+    try:
+        for v in documented:
+            assert lib.swc_set_tuning(b"lz_copier", v) == 0
+        for v in (2, -2):
+            assert lib.swc_set_tuning(b"lz_copier", v) != 0
+        for v in (1, 2):
+            assert lib.swc_set_tuning(b"bzip2_team_per_cu", v) != 0
+    finally:
+        assert lib.swc_set_tuning(b"lz_copier", 1) == 0
+
+
 def test_status_table_matches_header():
     hdr = open(os.path.join(ROOT, "include", "swc_status.h")).read()
     codes = {int(v) for v in re.findall(r"=\s*(\d+)", hdr)} - {0}

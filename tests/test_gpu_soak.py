@@ -96,7 +96,7 @@ def test_deflate_streams_over_spliced_text(seed):
 
 @pytest.mark.parametrize("seed", range(ROUNDS))
 def test_lzma2_units_of_random_encoder_settings(seed):
-    """The range decoder's decision is one block of gfx950 instructions (lzma_wave.h: SWC_LZMA_BIT_ASM): every lc / lp / pb,
+    """The range decoder's decision is one block of gfx950 instructions (lzma_wave.h: bit()): every lc / lp / pb,
     dictionaries from 4 KiB, both layouts of the literal coders."""
     from swcompression_amd import _lib
     lib = _lib.load()

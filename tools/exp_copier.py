@@ -1,5 +1,5 @@
-"""A/B of the LZ77 copy phase on the device: the byte-cell resolver (lz_copier=0) against the record-granular copier with an
-8 KiB / 16 KiB window (1 / 2), same batch, every unit verified after every mode.
+"""A/B of the LZ77 copy phase on the device: the byte-cell resolver (lz_copier=0) against the record-granular copier (1: the
+library's own choice by launch size, -1: the wave kernel always), same batch, every unit verified after every mode.
     python tools/exp_copier.py deflate64k|lz4_4m|deflate64k_mix [scale] [modes]"""
 import ctypes as C
 import os
@@ -14,7 +14,7 @@ from swcompression_amd import _lib
 
 name = sys.argv[1] if len(sys.argv) > 1 else "deflate64k"
 scale = float(sys.argv[2]) if len(sys.argv) > 2 else 1.0
-modes = [int(m) for m in sys.argv[3].split(",")] if len(sys.argv) > 3 else [0, 1, 2]
+modes = [int(m) for m in sys.argv[3].split(",")] if len(sys.argv) > 3 else [0, 1, -1]
 lib = _lib.load()
 w = bench.WORKLOADS[name]
 
