@@ -46,11 +46,15 @@ typedef enum swc_codec {
     SWC_CODEC_LZ4_COMPRESS = 7, /* ENCODE, one LZ4 block -- LZ4.compress(block:_:) LZ4+Compress.swift:157-281: in = prefix ++ block,
                               dict_len = length of the prefix (dictionary / previous block), out_cap >= n + n / 255 + 16;
                               A valid block for the same bytes, not the reference's bytes            */
-    SWC_CODEC_DEFLATE_COMPRESS = 8 /* ENCODE, one raw Deflate stream -- Deflate.compress(data:) Deflate+Compress.swift:22-213: one
+    SWC_CODEC_DEFLATE_COMPRESS = 8, /* ENCODE, one raw Deflate stream -- Deflate.compress(data:) Deflate+Compress.swift:22-213: one
                               stored or static-Huffman block over a greedy LZ77 parse; out_cap >= n + n / 8 + 32, out 4-byte
                               aligned; A valid stream for the same bytes, not the reference's bytes.  aux bit 0:
                               the unit is a SEGMENT of a longer stream -- BFINAL clear, an empty stored block behind the block, so
                               that the outputs of consecutive segments, the last one with aux = 0, are one stream           */
+    SWC_CODEC_DEFLATE_COMPRESS_DYNAMIC = 9 /* ENCODE, the job contract of 8 (the same parse, out_cap, alignment and aux bit 0); the
+                              block is dynamic-Huffman (BTYPE 10, its own code tables, 15-bit codes) where that is strictly
+                              smaller than the static block, and stored when not larger than the better of the two (an
+                              extension: the reference writes no dynamic block).  Where it is not dynamic, the bytes of 8  */
 } swc_codec;
 
 typedef struct swc_job {
@@ -150,6 +154,11 @@ int swc_lz4_compress(const uint8_t* data, size_t len, int independent_blocks, in
  * input (big endian; computed on the host). */
 int swc_deflate_compress(const uint8_t* data, size_t len, uint8_t** out, size_t* out_len);
 int swc_zlib_archive(const uint8_t* data, size_t len, uint8_t** out, size_t* out_len);
+/* The same with dynamic-Huffman blocks where they are smaller (SWC_CODEC_DEFLATE_COMPRESS_DYNAMIC: every unit and every
+ * segment is one block with its own code tables; never larger than the static form, its bytes where no block is dynamic).
+ * Parameters as swc_deflate_compress / swc_zlib_archive. */
+int swc_deflate_compress_dynamic(const uint8_t* data, size_t len, uint8_t** out, size_t* out_len);
+int swc_zlib_archive_dynamic(const uint8_t* data, size_t len, uint8_t** out, size_t* out_len);
 /* GzipArchive.archive(data:comment:fileName:writeHeaderCRC:isTextFile:osType:modificationTime:extraFields:)
  * GzipArchive.swift:126-240: the header as the reference writes it (magic, CM 8, flags, MTIME, XFL 2, OS, FEXTRA, FNAME,
  * FCOMMENT, FHCRC), Deflate.compress(data) on the device, CRC-32 and ISIZE.  comment / file_name: ISO Latin-1 bytes (NULL =
@@ -165,6 +174,10 @@ typedef struct swc_gzip_extra_field {
 int swc_gzip_archive(const uint8_t* data, size_t len, const uint8_t* comment, size_t comment_len, const uint8_t* file_name,
                      size_t file_name_len, int write_header_crc, int is_text_file, int os_type, int has_mtime, int64_t mtime,
                      const swc_gzip_extra_field* extra, size_t n_extra, uint8_t** out, size_t* out_len);
+/* The same with the body from swc_deflate_compress_dynamic.  Parameters as swc_gzip_archive. */
+int swc_gzip_archive_dynamic(const uint8_t* data, size_t len, const uint8_t* comment, size_t comment_len, const uint8_t* file_name,
+                             size_t file_name_len, int write_header_crc, int is_text_file, int os_type, int has_mtime, int64_t mtime,
+                             const swc_gzip_extra_field* extra, size_t n_extra, uint8_t** out, size_t* out_len);
 /* BZip2.compress(data:blockSize:) BZip2+Compress.swift:40-74 (BZip2.compress(data:) :19-21 = block_size 1).  block_size 1..9 =
  * BlockSize.one ... .nine (else SWC_E_INVALID_ARGUMENT); the input is cut into blocks of block_size x 80,000 bytes as the
  * reference cuts it (:46), all blocks are compressed on the device together: initial run-length coding, Burrows-Wheeler

@@ -202,10 +202,12 @@ class Deflate:
         return _call_simple("swc_deflate_decompress", data, consumed=True)
 
     @staticmethod
-    def compress(data):
+    def compress(data, dynamic=False):
         """Deflate.compress(data:) (Deflate+Compress.swift:22-46): one stored or static-Huffman block, compressed on the device.
-        The stream decodes to `data` with the reference's decoder; its bytes are not the reference encoder's."""
-        return _call_simple("swc_deflate_compress", data)
+        The stream decodes to `data` with the reference's decoder; its bytes are not the reference encoder's.
+        dynamic=True (an extension; Deflate.compress(data:dynamicHuffman:) in a Swift shim): the same parse, the block
+        dynamic-Huffman where that is smaller -- never larger than the default, its bytes where no block is dynamic."""
+        return _call_simple("swc_deflate_compress_dynamic" if dynamic else "swc_deflate_compress", data)
 
 
 class GzipArchive:
@@ -219,11 +221,11 @@ class GzipArchive:
 
     @staticmethod
     def archive(data, comment=None, file_name=None, write_header_crc=False, is_text_file=False, os_type=None,
-                modification_time=None, extra_fields=()):
+                modification_time=None, extra_fields=(), *, dynamic=False):
         """GzipArchive.archive(data:comment:fileName:writeHeaderCRC:isTextFile:osType:modificationTime:extraFields:)
         (GzipArchive.swift:126-240).  os_type: the header byte (0 FAT, 3 Unix, 7 Macintosh, 11 NTFS, None = 255 unknown:
         FileSystemType+Gzip.swift:23-36); modification_time: seconds since 1970; extra_fields: (si1, si2, bytes) triples.
-        The body is Deflate.compress(data) on the device."""
+        The body is Deflate.compress(data, dynamic=dynamic) on the device."""
         def latin1(text):
             if text is None:
                 return None, 0
@@ -248,10 +250,11 @@ class GzipArchive:
             cb = C.create_string_buffer(1).raw                          # a non-NULL pointer: an empty comment is a comment
         if fb is not None and fn == 0:
             fb = C.create_string_buffer(1).raw
-        st = lib.swc_gzip_archive(data, len(data), cb, cn, fb, fn, int(bool(write_header_crc)), int(bool(is_text_file)),
-                                  255 if os_type is None else int(os_type), 0 if modification_time is None else 1,
-                                  0 if modification_time is None else int(modification_time), C.cast(arr, C.c_void_p) if keep else None,
-                                  len(keep), C.byref(out), C.byref(n))
+        fn_archive = lib.swc_gzip_archive_dynamic if dynamic else lib.swc_gzip_archive
+        st = fn_archive(data, len(data), cb, cn, fb, fn, int(bool(write_header_crc)), int(bool(is_text_file)),
+                        255 if os_type is None else int(os_type), 0 if modification_time is None else 1,
+                        0 if modification_time is None else int(modification_time), C.cast(arr, C.c_void_p) if keep else None,
+                        len(keep), C.byref(out), C.byref(n))
         res = _take(out, n.value)
         if st:
             _raise(st, res)
@@ -264,9 +267,9 @@ class ZlibArchive:
         return _call_simple("swc_zlib_unarchive", archive)
 
     @staticmethod
-    def archive(data):
-        """ZlibArchive.archive(data:) (ZlibArchive.swift:54-70)."""
-        return _call_simple("swc_zlib_archive", data)
+    def archive(data, dynamic=False):
+        """ZlibArchive.archive(data:) (ZlibArchive.swift:54-70); dynamic=True: the body as Deflate.compress(data, dynamic=True)."""
+        return _call_simple("swc_zlib_archive_dynamic" if dynamic else "swc_zlib_archive", data)
 
 
 class BZip2:

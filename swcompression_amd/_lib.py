@@ -78,8 +78,11 @@ def load():
     sig("swc_deflate_compress", I, C.c_char_p, C.c_size_t, u8pp, szp)
     sig("swc_bzip2_compress", I, C.c_char_p, C.c_size_t, I, u8pp, szp)
     sig("swc_zlib_archive", I, C.c_char_p, C.c_size_t, u8pp, szp)
-    sig("swc_gzip_archive", I, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, I, I, I, I, C.c_int64,
-        C.c_void_p, C.c_size_t, u8pp, szp)
+    sig("swc_deflate_compress_dynamic", I, C.c_char_p, C.c_size_t, u8pp, szp)
+    sig("swc_zlib_archive_dynamic", I, C.c_char_p, C.c_size_t, u8pp, szp)
+    for n in ("swc_gzip_archive", "swc_gzip_archive_dynamic"):
+        sig(n, I, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, I, I, I, I, C.c_int64,
+            C.c_void_p, C.c_size_t, u8pp, szp)
     sig("swc_lz4_compress", I, C.c_char_p, C.c_size_t, I, I, I, I, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int64, u8pp, szp)
     sig("swc_zip_get_entries_data", I, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t)
     sig("swc_stat", C.c_longlong, C.c_char_p)

@@ -39,6 +39,7 @@
 
 #include "swc_common.h"
 #include "simt.h"
+#include "huffman_wave.h"
 
 namespace swc {
 namespace bz2c {
@@ -83,13 +84,7 @@ SWC_D void lds_or(uint32_t* p, uint32_t v) {
     *p |= v;
 #endif
 }
-SWC_D void lds_inc(uint32_t* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-    *p += 1u;
-#endif
-}
+using huff::lds_inc;
 SWC_D void global_or(SWC_AS_GLOBAL uint32_t* p, uint32_t v) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -507,83 +502,9 @@ struct GroupCost {     // a wavefront per kGroupsPerWave groups of a block
         SIMT_END
     }
 };
-struct HuffLds {
-    uint32_t w[kSymStride];          // weights
-    uint32_t order[kSymStride];      // symbols by weight
-    uint32_t wt[kSymStride];         // inner nodes, in order of creation (= of weight)
-    uint32_t parent_leaf[kSymStride];
-    uint32_t parent_inner[kSymStride];
-    uint32_t depth_inner[kSymStride];
-    uint32_t len[kSymStride];
-    uint32_t count[24], base[24];
-};
-// Code lengths (no code longer than max_len: weights halved until that holds, as bzip2's hbMakeCodeLengths does) and canonical
-// codes of one table from the counts of its symbols; a symbol that does not occur counts as one.
-template <int N>
-SWC_D void huffman_wave(HuffLds* l, uint32_t alpha, uint32_t max_len) {
-    using simt::PT;
-    for (;;) {
-        // ---- the symbols in order of weight (ties: by symbol): every lane ranks its symbols against all
-        SIMT_BEGIN(t, N)
-            for (uint32_t s = (uint32_t)t; s < alpha; s += (uint32_t)N) {
-                const uint32_t ws = l->w[s];
-                uint32_t r = 0;
-                for (uint32_t k = 0; k < alpha; k++) { const uint32_t wk = l->w[k]; r += wk < ws || (wk == ws && k < s) ? 1u : 0u; }
-                l->order[r] = s;
-            }
-        SIMT_END_WAVE
-        // ---- two queues: the lightest two of (next leaf, next inner node) are joined; inner nodes come into being in order of weight
-        uint32_t made = 0;
-        SIMT_BEGIN(t, N)
-            if (t == 0) {
-                uint32_t nl = 0, ni = 0, m = 0;
-                while (alpha - nl + m - ni > 1u) {
-                    uint32_t sum = 0;
-                    for (int k = 0; k < 2; k++) {
-                        if (nl < alpha && (ni >= m || l->w[l->order[nl]] <= l->wt[ni])) { const uint32_t s = l->order[nl++]; l->parent_leaf[s] = m; sum += l->w[s]; }
-                        else { l->parent_inner[ni] = m; sum += l->wt[ni++]; }
-                    }
-                    l->wt[m] = sum;
-                    l->parent_inner[m] = 0xFFFFFFFFu;
-                    m++;
-                }
-                for (uint32_t k = m; k-- > 0u;) l->depth_inner[k] = l->parent_inner[k] == 0xFFFFFFFFu ? 0u : l->depth_inner[l->parent_inner[k]] + 1u;
-                l->count[23] = m;
-            }
-        SIMT_END_WAVE
-        made = l->count[23];
-        PT<uint32_t, N> mx;
-        SIMT_BEGIN(t, N)
-            uint32_t m = 0;
-            for (uint32_t s = (uint32_t)t; s < alpha; s += (uint32_t)N) {
-                const uint32_t d = made ? l->depth_inner[l->parent_leaf[s]] + 1u : 1u;
-                l->len[s] = d;
-                m = d > m ? d : m;
-            }
-            mx[t] = m;
-        SIMT_END_WAVE
-        simt::wave_scan_max_incl<N>(mx);
-        if (simt::wave_read<N>(mx, N - 1) <= max_len) break;
-        SIMT_BEGIN(t, N) for (uint32_t s = (uint32_t)t; s < alpha; s += (uint32_t)N) l->w[s] = l->w[s] / 2u + 1u; SIMT_END_WAVE
-    }
-    // ---- canonical codes: in order of (length, symbol)
-    SIMT_BEGIN(t, N) if (t < 24) l->count[t] = 0u; SIMT_END_WAVE
-    SIMT_BEGIN(t, N) for (uint32_t s = (uint32_t)t; s < alpha; s += (uint32_t)N) lds_inc(&l->count[l->len[s]]); SIMT_END_WAVE
-    SIMT_BEGIN(t, N)
-        if (t == 0) {
-            uint32_t next = 0;
-            for (uint32_t k = 1; k <= max_len; k++) { l->base[k] = next; next = (next + l->count[k]) << 1; }
-        }
-    SIMT_END_WAVE
-    SIMT_BEGIN(t, N)
-        for (uint32_t s = (uint32_t)t; s < alpha; s += (uint32_t)N) {
-            const uint32_t ls = l->len[s];
-            uint32_t r = 0;
-            for (uint32_t k = 0; k < s; k++) r += l->len[k] == ls ? 1u : 0u;
-            l->wt[s] = (l->base[ls] + r) | (ls << 24);        // (the inner weights are not needed any more)
-        }
-    SIMT_END_WAVE
-}
+// the shared builder (huffman_wave.h) at bzip2's alphabet
+typedef huff::HuffLds<kSymStride> HuffLds;
+using huff::huffman_wave;
 struct Huff {          // a wavefront per (block, table)
     Segs c;
     typedef HuffLds Lds;

@@ -342,8 +342,10 @@ int swc_gzip_multi_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, si
 // block (Deflate.swift:30-249).  What is given up: matches across a segment's start (under 0.1 % of the size at 256 KiB), and
 // the reference's "one block" shape -- which SURVEY 8f-4 does not ask to keep.  Buffers of up to kCompressWhole bytes stay ONE
 // block, as the reference writes them.
+// `codec`: SWC_CODEC_DEFLATE_COMPRESS, or SWC_CODEC_DEFLATE_COMPRESS_DYNAMIC -- the same units and segments, every one a block with
+// its own code tables where that is smaller (the _dynamic entry points below).
 constexpr size_t kCompressWhole = (size_t)1 << 20, kCompressSegment = (size_t)256 << 10;
-static int deflate_compress_unit(const uint8_t* data, size_t len, HostUnit& u) {
+static int deflate_compress_unit(int codec, const uint8_t* data, size_t len, HostUnit& u) {
     if (len > kCompressWhole) {
         const size_t nseg = (len + kCompressSegment - 1) / kCompressSegment;
         std::vector<HostUnit> segs(nseg);
@@ -356,7 +358,7 @@ static int deflate_compress_unit(const uint8_t* data, size_t len, HostUnit& u) {
             s.cap_exact = true;
             s.aux = k + 1 < nseg ? 1 : 0;
         }
-        const int st = run_units(SWC_CODEC_DEFLATE_COMPRESS, segs);
+        const int st = run_units(codec, segs);
         if (st != SWC_OK) return st;
         size_t total = 0;
         for (const HostUnit& s : segs) { if (s.status != SWC_OK) { u.status = s.status; return SWC_OK; } total += s.size(); }
@@ -371,12 +373,12 @@ static int deflate_compress_unit(const uint8_t* data, size_t len, HostUnit& u) {
     u.in = data; u.in_len = len;
     u.cap_hint = len + len / 8 + 16;
     u.cap_exact = true;
-    return run_one(SWC_CODEC_DEFLATE_COMPRESS, u);
+    return run_one(codec, u);
 }
-int swc_deflate_compress(const uint8_t* data, size_t len, uint8_t** out, size_t* out_len) try {
+static int deflate_compress_impl(int codec, const uint8_t* data, size_t len, uint8_t** out, size_t* out_len) try {
     if (!out || !out_len || (len && !data)) return SWC_E_INVALID_ARGUMENT;
     HostUnit u;
-    int st = deflate_compress_unit(data, len, u);
+    int st = deflate_compress_unit(codec, data, len, u);
     if (st == SWC_OK) st = u.status;
     if (st) { give_empty(out, out_len); return st; }
     give(u.out, out, out_len);
@@ -385,10 +387,16 @@ int swc_deflate_compress(const uint8_t* data, size_t len, uint8_t** out, size_t*
     if (out && out_len) give_empty(out, out_len);
     return SWC_E_DEVICE;
 }
+int swc_deflate_compress(const uint8_t* data, size_t len, uint8_t** out, size_t* out_len) {
+    return deflate_compress_impl(SWC_CODEC_DEFLATE_COMPRESS, data, len, out, out_len);
+}
+int swc_deflate_compress_dynamic(const uint8_t* data, size_t len, uint8_t** out, size_t* out_len) {
+    return deflate_compress_impl(SWC_CODEC_DEFLATE_COMPRESS_DYNAMIC, data, len, out, out_len);
+}
 // GzipArchive.archive(data:comment:fileName:writeHeaderCRC:isTextFile:osType:modificationTime:extraFields:) (GzipArchive.swift:126-240)
-int swc_gzip_archive(const uint8_t* data, size_t len, const uint8_t* comment, size_t comment_len, const uint8_t* file_name,
-                     size_t file_name_len, int write_header_crc, int is_text_file, int os_type, int has_mtime, int64_t mtime,
-                     const swc_gzip_extra_field* extra, size_t n_extra, uint8_t** out, size_t* out_len) try {
+static int gzip_archive_impl(int codec, const uint8_t* data, size_t len, const uint8_t* comment, size_t comment_len, const uint8_t* file_name,
+                             size_t file_name_len, int write_header_crc, int is_text_file, int os_type, int has_mtime, int64_t mtime,
+                             const swc_gzip_extra_field* extra, size_t n_extra, uint8_t** out, size_t* out_len) try {
     if (!out || !out_len || (len && !data) || (comment_len && !comment) || (file_name_len && !file_name) || (n_extra && !extra))
         return SWC_E_INVALID_ARGUMENT;
     uint8_t flags = 0;
@@ -430,7 +438,7 @@ int swc_gzip_archive(const uint8_t* data, size_t len, const uint8_t* comment, si
         z.push_back((uint8_t)(h >> 8));
     }
     HostUnit u;
-    int st = deflate_compress_unit(data, len, u);                      // :223
+    int st = deflate_compress_unit(codec, data, len, u);               // :223
     if (st == SWC_OK) st = u.status;
     if (st) { give_empty(out, out_len); return st; }
     z.insert(z.end(), u.out.begin(), u.out.end());
@@ -444,11 +452,23 @@ int swc_gzip_archive(const uint8_t* data, size_t len, const uint8_t* comment, si
     if (out && out_len) give_empty(out, out_len);
     return SWC_E_DEVICE;
 }
+int swc_gzip_archive(const uint8_t* data, size_t len, const uint8_t* comment, size_t comment_len, const uint8_t* file_name,
+                     size_t file_name_len, int write_header_crc, int is_text_file, int os_type, int has_mtime, int64_t mtime,
+                     const swc_gzip_extra_field* extra, size_t n_extra, uint8_t** out, size_t* out_len) {
+    return gzip_archive_impl(SWC_CODEC_DEFLATE_COMPRESS, data, len, comment, comment_len, file_name, file_name_len, write_header_crc,
+                             is_text_file, os_type, has_mtime, mtime, extra, n_extra, out, out_len);
+}
+int swc_gzip_archive_dynamic(const uint8_t* data, size_t len, const uint8_t* comment, size_t comment_len, const uint8_t* file_name,
+                             size_t file_name_len, int write_header_crc, int is_text_file, int os_type, int has_mtime, int64_t mtime,
+                             const swc_gzip_extra_field* extra, size_t n_extra, uint8_t** out, size_t* out_len) {
+    return gzip_archive_impl(SWC_CODEC_DEFLATE_COMPRESS_DYNAMIC, data, len, comment, comment_len, file_name, file_name_len, write_header_crc,
+                             is_text_file, os_type, has_mtime, mtime, extra, n_extra, out, out_len);
+}
 // ZlibArchive.archive(data:) (ZlibArchive.swift:54-70)
-int swc_zlib_archive(const uint8_t* data, size_t len, uint8_t** out, size_t* out_len) try {
+static int zlib_archive_impl(int codec, const uint8_t* data, size_t len, uint8_t** out, size_t* out_len) try {
     if (!out || !out_len || (len && !data)) return SWC_E_INVALID_ARGUMENT;
     HostUnit u;
-    int st = deflate_compress_unit(data, len, u);
+    int st = deflate_compress_unit(codec, data, len, u);
     if (st == SWC_OK) st = u.status;
     if (st) { give_empty(out, out_len); return st; }
     std::vector<uint8_t> z;
@@ -463,6 +483,12 @@ int swc_zlib_archive(const uint8_t* data, size_t len, uint8_t** out, size_t* out
 } catch (...) {
     if (out && out_len) give_empty(out, out_len);
     return SWC_E_DEVICE;
+}
+int swc_zlib_archive(const uint8_t* data, size_t len, uint8_t** out, size_t* out_len) {
+    return zlib_archive_impl(SWC_CODEC_DEFLATE_COMPRESS, data, len, out, out_len);
+}
+int swc_zlib_archive_dynamic(const uint8_t* data, size_t len, uint8_t** out, size_t* out_len) {
+    return zlib_archive_impl(SWC_CODEC_DEFLATE_COMPRESS_DYNAMIC, data, len, out, out_len);
 }
 
 int swc_zlib_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, size_t* out_len) try {

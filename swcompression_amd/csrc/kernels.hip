@@ -388,6 +388,24 @@ hipError_t launch_deflate_compress(Job* jobs, size_t n, hipStream_t stream) {
     g_pt.mark(stream);
     return hipGetLastError();
 }
+// ... dynamic blocks where they are smaller (deflate_comp.h: the parse twice, counted then emitted): a kernel of its own, its LDS
+// (10.5 KB: the code tables beside the hash table) is not the static kernel's
+__global__ __launch_bounds__(64) void swc_deflate_compress_dynamic_kernel(Job* __restrict__ jobs, uint32_t n, const uint32_t* __restrict__ order) {
+    __shared__ __attribute__((aligned(16))) defc::DynLds lds;
+    uint32_t g = job_of(order, blockIdx.x, n);
+    if (g >= n) return;
+    Job job = jobs[g];
+    defc::deflate_compress_dynamic_job<kWave>(job, &lds);
+    if (threadIdx.x == 0) put_result(jobs, g, job);
+}
+hipError_t launch_deflate_compress_dynamic(Job* jobs, size_t n, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    g_pt.begin(stream);
+    const uint32_t* order = job_order(jobs, n, stream);
+    hipLaunchKernelGGL(swc_deflate_compress_dynamic_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, jobs, (uint32_t)n, order);
+    g_pt.mark(stream);
+    return hipGetLastError();
+}
 
 // ---- LZMA / LZMA2, one stream per wavefront ---------------------------------------------------------
 // LDS: the u16 probability cells of one stream.  With the workspace (spill area for big literal coders) at hand the
