@@ -194,10 +194,6 @@ struct MsbReader {
     }
 };
 
-#if defined(__HIP_DEVICE_COMPILE__)
-SWC_D uint32_t wave_count(bool pred) { return (uint32_t)__popcll(__ballot(pred)); }
-#endif
-
 // ---- stage 3a, first part: the walk of the segments, RESUMABLE ------------------------------------------------------------
 // Every lane walks segments (v = P[cur]; byte = v & 255; cur = v >> 8) until none is left.  One call of walk_tick() takes
 // every lane ONE step: it consumes the pointer loaded by the call before, and issues the next load without waiting for it --
@@ -272,7 +268,7 @@ SWC_HD bool walk_tick(Walk& W) {
     }
     if (W.active) { W.v = W.ws.P[W.cur]; W.pending = true; }
 #if defined(__HIP_DEVICE_COMPILE__)
-    return WAVE > 1 ? __ballot(W.active) == 0ull : !W.active;
+    return WAVE > 1 ? __ballot(W.active) == 0ull : !W.active;   // (through simt::lane_ballot the kernel comes out different: left as it was)
 #else
     return !W.active;
 #endif
@@ -293,9 +289,7 @@ struct Stage1 {
     // architectural) and the value is broadcast, so no cross-lane memory visibility is assumed.
     SWC_HD int selector_at(int i) {
         int v = lane == 0 ? (int)ws.selectors[i] : 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-        if (WAVE > 1) v = __builtin_amdgcn_readfirstlane(v);
-#endif
+        if (WAVE > 1) v = (int)simt::uniform((uint32_t)v);
         return v;
     }
 
@@ -341,7 +335,7 @@ struct Stage1 {
         if (!over) {
 #if defined(__HIP_DEVICE_COMPILE__)
             if (WAVE > 1) {
-                len = 1 + wave_count(lane >= 1 && lane <= kMaxLen && c >= my_lim);
+                len = 1 + simt::lane_count(lane >= 1 && lane <= kMaxLen && c >= my_lim);
             } else
 #endif
             {

@@ -77,21 +77,6 @@ SWC_HD uint32_t rle1_bound(uint32_t n) { return align16(n + n / 4u + 16u); }
 // every symbol at 20 bits; the header: 18002 selector bits, two tables of 258 x 39 bits at most
 SWC_HD uint32_t out_bound(uint32_t n_rle) { return align16((n_rle + 16u) / 8u * 20u + 8192u); }
 
-SWC_D void lds_or(uint32_t* p, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-    *p |= v;
-#endif
-}
-using huff::lds_inc;
-SWC_D void global_or(SWC_AS_GLOBAL uint32_t* p, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    *p |= v;
-#endif
-}
 SWC_HD uint32_t bswap32(uint32_t v) { return (v >> 24) | ((v >> 8) & 0xFF00u) | ((v << 8) & 0xFF0000u) | (v << 24); }
 
 // ================================================================================================================ rle1
@@ -181,20 +166,6 @@ struct Segs {
     uint32_t nb, stream_cap, lead;            // lead: the first block starts at this bit (the stream so far ends inside a dword)
     uint32_t cost_waves;                      // table choice: wavefronts per block in the grid
 };
-SWC_D void lds_max(uint32_t* p, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-    if (v > *p) *p = v;
-#endif
-}
-SWC_D void global_add(SWC_AS_GLOBAL uint32_t* p, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    *p += v;
-#endif
-}
 struct NoLds { uint32_t unused; };
 struct SegLastLds { uint32_t tab[256]; };
 struct SegLast {       // a wavefront per segment
@@ -205,7 +176,7 @@ struct SegLast {       // a wavefront per segment
         const uint32_t lo = (s - c.seg_off[b]) * kSeg, hi = lo + kSeg < n ? lo + kSeg : n;
         SIMT_BEGIN(t, N) for (uint32_t i = (uint32_t)t; i < 256u; i += (uint32_t)N) lds->tab[i] = 0u; SIMT_END_WAVE
         SIMT_BEGIN(t, N)
-            for (uint32_t i = lo + (uint32_t)t; i < hi; i += (uint32_t)N) lds_max(&lds->tab[c.col[base + i]], i + 1u);
+            for (uint32_t i = lo + (uint32_t)t; i < hi; i += (uint32_t)N) simt::lds_max(&lds->tab[c.col[base + i]], i + 1u);
         SIMT_END_WAVE
         SIMT_BEGIN(t, N) for (uint32_t i = (uint32_t)t; i < 256u; i += (uint32_t)N) c.last[256u * s + i] = lds->tab[i]; SIMT_END
     }
@@ -244,7 +215,7 @@ struct MtfOut {
     SWC_D void flush() {
         const uint32_t k = nstage, o = nsym;
         SIMT_BEGIN(t, N)
-            if ((uint32_t)t < k) { out[o + (uint32_t)t] = (uint16_t)stage[t]; lds_inc(&l->freq[stage[t]]); }
+            if ((uint32_t)t < k) { out[o + (uint32_t)t] = (uint16_t)stage[t]; simt::lds_add(&l->freq[stage[t]], 1u); }
         SIMT_END_WAVE
         nsym += k;
         nstage = 0;
@@ -408,8 +379,8 @@ struct MtfSeg {        // a wavefront per segment
         if (m.nstage) m.flush();
         const uint32_t nsym = m.nsym;
         SIMT_BEGIN(t, N)
-            for (uint32_t i = (uint32_t)t; i < kMaxSyms + 2u; i += (uint32_t)N) if (lds->freq[i]) global_add(&info->freq[i], lds->freq[i]);
-            if (t == 0) { c.seg_nsym[s] = nsym; global_add(&info->n_sym, nsym); }
+            for (uint32_t i = (uint32_t)t; i < kMaxSyms + 2u; i += (uint32_t)N) if (lds->freq[i]) simt::global_add(&info->freq[i], lds->freq[i]);
+            if (t == 0) { c.seg_nsym[s] = nsym; simt::global_add(&info->n_sym, nsym); }
         SIMT_END_WAVE
     }
 };
@@ -490,14 +461,14 @@ struct GroupCost {     // a wavefront per kGroupsPerWave groups of a block
                     if (ck < cost) { cost = ck; best = k; }
                 }
                 sel[g] = (uint8_t)best;
-                for (uint32_t i = lo; i < hi; i++) lds_inc(&lds->rfreq[best][sy[i]]);
+                for (uint32_t i = lo; i < hi; i++) simt::lds_add(&lds->rfreq[best][sy[i]], 1u);
             }
         SIMT_END_WAVE
         SWC_AS_GLOBAL uint32_t* rf = c.rfreq + (size_t)b * kMaxTables * kSymStride;
         SIMT_BEGIN(t, N)
             for (uint32_t i = (uint32_t)t; i < kMaxTables * kSymStride; i += (uint32_t)N) {
                 const uint32_t v = (&lds->rfreq[0][0])[i];
-                if (v) global_add(rf + i, v);
+                if (v) simt::global_add(rf + i, v);
             }
         SIMT_END
     }
@@ -555,7 +526,7 @@ struct Emitter {
                 const uint32_t b = 4u * (o0 + i);
                 const uint32_t v = bswap32(l->stage[i]);        // the stream's first bit is the top bit of byte 0
                 if (b + 4u > cap) continue;
-                if (o0 + i == f || (all && i + 1u == nd)) global_or((SWC_AS_GLOBAL uint32_t*)(out + b), v);   // shared with a neighbour
+                if (o0 + i == f || (all && i + 1u == nd)) simt::global_or((SWC_AS_GLOBAL uint32_t*)(out + b), v);   // shared with a neighbour
                 else *(SWC_AS_GLOBAL uint32_t*)(out + b) = v;
             }
             carry[t] = l->stage[nd];
@@ -577,11 +548,11 @@ struct Emitter {
             if (n != 0u) {
                 const uint32_t b = f0 + x[t] - n, d = b >> 5, s = b & 31u;      // s bits of dword d are taken
                 const uint32_t c = n == 32u ? code[t] : code[t] & ((1u << n) - 1u);
-                if (s + n <= 32u) lds_or(&l->stage[d], c << (32u - s - n));
+                if (s + n <= 32u) simt::lds_or(&l->stage[d], c << (32u - s - n));
                 else {
                     const uint32_t lo = s + n - 32u;                              // bits that go to the next dword
-                    lds_or(&l->stage[d], c >> lo);
-                    lds_or(&l->stage[d + 1u], c << (32u - lo));
+                    simt::lds_or(&l->stage[d], c >> lo);
+                    simt::lds_or(&l->stage[d + 1u], c << (32u - lo));
                 }
             }
         SIMT_END_WAVE

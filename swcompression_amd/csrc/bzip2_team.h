@@ -89,10 +89,7 @@ SWC_HD void team_prep(uint8_t* ws_base, size_t lcap, uint32_t n_blocks, uint32_t
             w = carve(ws_base, b, lcap);
             if (team_walkable(w)) { Cut c; c.set(w.hdr->n, w.hdr->orig_ptr); segs = c.segs; }
         }
-        uint32_t incl = segs;
-#if defined(__HIP_DEVICE_COMPILE__)
-        incl = simt::wave_scan_incl_dev(segs);
-#endif
+        const uint32_t incl = simt::wave_scan_incl_dev(segs);
         if (b < n_blocks) {
             const TeamSegs t = team_segs(w);
             t.words[kTwSegs] = segs;
@@ -100,11 +97,7 @@ SWC_HD void team_prep(uint8_t* ws_base, size_t lcap, uint32_t n_blocks, uint32_t
             t.words[kTwBad] = 0;
             w.hdr->pad = kWalkNone;
         }
-#if defined(__HIP_DEVICE_COMPILE__)
-        before += (uint32_t)__builtin_amdgcn_readlane((int)incl, WAVE - 1);
-#else
-        before += incl;
-#endif
+        before += simt::lane_read(incl, WAVE - 1);
     }
     if (lane == 0) {
         const TeamSegs t0 = team_segs(carve(ws_base, 0, lcap));
@@ -114,20 +107,6 @@ SWC_HD void team_prep(uint8_t* ws_base, size_t lcap, uint32_t n_blocks, uint32_t
 }
 
 // ---- team_walk: every thread of the team draws tickets until there are none -------------------------------------------------
-SWC_HD uint32_t team_ticket(SWC_AS_GLOBAL uint32_t* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    return (*p)++;
-#endif
-}
-SWC_HD void store_u64_stream(gptr p, uint64_t v) {   // past the caches: the segment buffers are read once, much later
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_nontemporal_store(v, (SWC_AS_GLOBAL uint64_t*)p);
-#else
-    store_u64(p, v);
-#endif
-}
 // (`home`: the team of the XCD the thread runs on.  A thread whose team has no tickets left goes on with the next team's: the
 // walk is complete whatever the workgroups' spread over the XCDs was, and the last blocks of a launch are shared.)
 SWC_HD void team_walk(uint8_t* ws_base, size_t lcap, uint32_t n_blocks, uint32_t home) {
@@ -143,7 +122,7 @@ SWC_HD void team_walk(uint8_t* ws_base, size_t lcap, uint32_t n_blocks, uint32_t
         TeamSegs ts;
         Cut c;
         for (;;) {
-            const uint32_t t = team_ticket(counter);
+            const uint32_t t = simt::global_add(counter, 1u);
             if (t >= total) break;
             // the block of the ticket: tickets only grow, so the search goes on from the last block
             bool lost = false;
@@ -288,11 +267,7 @@ SWC_HD void team_finish(Job& job, Workspace ws, FinishLds* l, int lane) {
             }
         }
         if (len > c.cap && sub == 0u) {
-#if defined(__HIP_DEVICE_COMPILE__)
-            const uint32_t e = __hip_atomic_fetch_add(&l->n_over, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-            const uint32_t e = l->n_over++;
-#endif
+            const uint32_t e = simt::lds_add(&l->n_over, 1u);
             if (e < kOver) l->a.over[e] = (uint16_t)q;
         }
     }

@@ -54,13 +54,6 @@ SWC_HD uint32_t hash3(uint32_t w) { return ((w & 0xFFFFFFu) * 2654435761u) >> (3
 // the largest stream `n` bytes can turn into: a static block of nine-bit literals, or the stored block
 SWC_HD uint64_t bound(uint64_t n) { return n + n / 8 + 16; }
 SWC_HD uint32_t rev_bits(uint32_t v, uint32_t n) { return brev32(v) >> (32u - n); }
-SWC_HD uint32_t log2u(uint32_t v) {   // floor(log2 v), v != 0
-#if defined(__HIP_DEVICE_COMPILE__)
-    return 31u - (uint32_t)__clz((int)v);
-#else
-    return 31u - (uint32_t)__builtin_clz(v);
-#endif
-}
 // static code of a literal byte: (bits, count), most significant code bit first in the stream (RFC 1951 3.2.6)
 SWC_HD void literal_code(uint32_t v, uint32_t& code, uint32_t& nb) {
     if (v < 144u) { code = rev_bits(0x30u + v, 8); nb = 8; }
@@ -132,13 +125,6 @@ struct Compressor {
     const uint32_t* clc = nullptr;
     uint32_t hlit = 0, hdist = 0, hclen = 0, ntok = 0;
 
-    SWC_D static void lds_or(uint32_t* p, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-        *p |= v;
-#endif
-    }
     // whole dwords of the stage -> out; the incomplete one moves to the front (`all`: the incomplete one too, at the end)
     SWC_D void flush(bool all) {
         const uint32_t nd = all ? (fill + 31u) >> 5 : fill >> 5;
@@ -168,8 +154,8 @@ struct Compressor {
         SIMT_BEGIN(t, N)
             if (nb[t] != 0u) {
                 const uint32_t b = f0 + x[t] - nb[t], d = b >> 5, s = b & 31u;
-                lds_or(&l->stage[d], code[t] << s);
-                if (s + nb[t] > 32u) lds_or(&l->stage[d + 1u], code[t] >> (32u - s));
+                simt::lds_or(&l->stage[d], code[t] << s);
+                if (s + nb[t] > 32u) simt::lds_or(&l->stage[d + 1u], code[t] >> (32u - s));
             }
         SIMT_END_WAVE
         const uint32_t total = simt::wave_read<N>(x, N - 1);
@@ -188,7 +174,7 @@ struct Compressor {
                 distance_sym(dist, ds, de, dx);
                 if constexpr (M == kCount) {
                     uint32_t* const f = sym;
-                    SIMT_BEGIN(t, N) if (t == 0) { huff::lds_inc(&f[ls]); huff::lds_inc(&f[kLitLen + ds]); } SIMT_END
+                    SIMT_BEGIN(t, N) if (t == 0) { simt::lds_add(&f[ls], 1u); simt::lds_add(&f[kLitLen + ds], 1u); } SIMT_END
                     xbits += le + de;
                 } else {
                     const uint32_t a = sym[ls], b = sym[kLitLen + ds];
@@ -201,8 +187,8 @@ struct Compressor {
             uint32_t* const f = sym;
             gcptr s = src;
             SIMT_BEGIN(t, N)
-                for (uint64_t i = (uint32_t)t; i < lit; i += (uint64_t)N) huff::lds_inc(&f[s[from + i]]);
-                if (t == 0 && eob) huff::lds_inc(&f[256]);
+                for (uint64_t i = (uint32_t)t; i < lit; i += (uint64_t)N) simt::lds_add(&f[s[from + i]], 1u);
+                if (t == 0 && eob) simt::lds_add(&f[256], 1u);
             SIMT_END_WAVE
             return;
         }

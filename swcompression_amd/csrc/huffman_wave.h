@@ -14,14 +14,6 @@
 namespace swc {
 namespace huff {
 
-SWC_D void lds_inc(uint32_t* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-    *p += 1u;
-#endif
-}
-
 // LDS of one build for an alphabet of up to CAP symbols (7 x CAP + 48 words)
 template <uint32_t CAP>
 struct HuffLds {
@@ -85,7 +77,7 @@ SWC_D void huffman_wave(HuffLds<CAP>* l, uint32_t alpha, uint32_t max_len) {
     }
     // ---- canonical codes: in order of (length, symbol)
     SIMT_BEGIN(t, N) if (t < 24) l->count[t] = 0u; SIMT_END_WAVE
-    SIMT_BEGIN(t, N) for (uint32_t s = (uint32_t)t; s < alpha; s += (uint32_t)N) lds_inc(&l->count[l->len[s]]); SIMT_END_WAVE
+    SIMT_BEGIN(t, N) for (uint32_t s = (uint32_t)t; s < alpha; s += (uint32_t)N) simt::lds_add(&l->count[l->len[s]], 1u); SIMT_END_WAVE
     SIMT_BEGIN(t, N)
         if (t == 0) {
             uint32_t next = 0;

@@ -185,86 +185,6 @@ struct SyncProf {};
 #define SWC_SPC(pp, k, n)
 #endif
 
-SWC_HD uint32_t funnel32(uint32_t hi, uint32_t lo, uint32_t sh) {  // bits [sh, sh + 32) of hi:lo; only sh % 32 counts
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_alignbit(hi, lo, sh);
-#else
-    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (sh & 31u));
-#endif
-}
-SWC_HD uint32_t bfe32(uint32_t v, uint32_t off, uint32_t width) {   // only off % 32 and width % 32 count; width 0 -> 0
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_ubfe(v, off, width);
-#else
-    off &= 31u; width &= 31u;
-    return width == 0 ? 0u : (v >> off) & ((1u << width) - 1u);
-#endif
-}
-SWC_HD uint32_t sbfe1(uint32_t v, uint32_t bit) {   // all ones if the bit is set
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (uint32_t)__builtin_amdgcn_sbfe((int)v, bit, 1u);
-#else
-    return (v >> bit) & 1u ? 0xFFFFFFFFu : 0u;
-#endif
-}
-SWC_HD uint32_t bfi32(uint32_t m, uint32_t a, uint32_t b) {   // (a & m) | (b & ~m) as v_bfi_b32 (the optimiser turns the C form into a compare and a select when m is a sign mask)
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint32_t d;
-    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(d) : "v"(m), "v"(a), "v"(b));
-    return d;
-#else
-    return (a & m) | (b & ~m);
-#endif
-}
-SWC_HD uint32_t alignbyte32(uint32_t hi, uint32_t lo, uint32_t nbytes) {   // bytes [n, n + 4) of hi:lo, n = nbytes % 4
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_alignbyte(hi, lo, nbytes);
-#else
-    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8u * (nbytes & 3u)));
-#endif
-}
-// (a << K) + b as ONE instruction (v_lshl_add_u32): the optimiser otherwise regroups sums of shifted terms into more of them
-template <int K>
-SWC_HD uint32_t lshl_add(uint32_t a, uint32_t b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint32_t d;
-    asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "n"(K), "v"(b));
-    return d;
-#else
-    return (a << K) + b;
-#endif
-}
-// (a & m) | o as ONE instruction (v_and_or_b32) with both constants in registers (a VOP3 instruction of gfx9 takes no literal)
-SWC_HD uint32_t and_or(uint32_t a, uint32_t m, uint32_t o) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint32_t d;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(m), "v"(o));
-    return d;
-#else
-    return (a & m) | o;
-#endif
-}
-// m ? 0 : b for a mask m of all ones or all zeros (v_bfi_b32 with the constant 0: the optimiser turns the C form into a compare and a select)
-SWC_HD uint32_t clear_if(uint32_t m, uint32_t b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint32_t d;
-    asm("v_bfi_b32 %0, %1, 0, %2" : "=v"(d) : "v"(m), "v"(b));
-    return d;
-#else
-    return b & ~m;
-#endif
-}
-// a * k + b, a signed 24-bit multiply-add (v_mad_i32_i24)
-SWC_HD uint32_t mad24(uint32_t a, int32_t k, uint32_t b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint32_t d;
-    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(k), "v"(b));
-    return d;
-#else
-    return (uint32_t)((int32_t)a * k) + b;
-#endif
-}
-
 // Where the subtables of the stream are: in LDS (g == nullptr) or in the workspace.
 struct SubTab {
     const SWC_AS_GLOBAL uint32_t* g;

@@ -84,74 +84,6 @@ inline uint64_t g_lz4_stats[8];   // emulated parser: rounds, lane parses, passe
 #define SWC_LZ4_STAT(i, n) ((void)0)
 #endif
 
-template <int W>
-struct Wave {
-    int lane;
-    SWC_D uint64_t ballot(bool p) const {
-#if defined(__HIP_DEVICE_COMPILE__)
-        return __ballot(p);
-#else
-        return p ? 1ull : 0ull;
-#endif
-    }
-    // value of lane `i` (i wave-uniform)
-    SWC_D uint32_t read(uint32_t v, uint32_t i) const {
-#if defined(__HIP_DEVICE_COMPILE__)
-        return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)i);
-#else
-        (void)i;
-        return v;
-#endif
-    }
-    SWC_D uint32_t first(uint32_t v) const {
-#if defined(__HIP_DEVICE_COMPILE__)
-        return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-#else
-        return v;
-#endif
-    }
-    SWC_D uint32_t scan_incl(uint32_t x) const {
-#if defined(__HIP_DEVICE_COMPILE__)
-        x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);
-        x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);
-        x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false);
-        x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);
-        x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);
-        x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);
-#endif
-        return x;
-    }
-};
-
-SWC_HD int popc64(uint64_t m) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __popcll(m);
-#else
-    return __builtin_popcountll(m);
-#endif
-}
-SWC_HD int ctz64(uint64_t m) {   // m != 0
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __ffsll((long long)m) - 1;
-#else
-    return __builtin_ctzll(m);
-#endif
-}
-SWC_HD int clz64(uint64_t m) {   // m != 0
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __clzll((long long)m);
-#else
-    return __builtin_clzll(m);
-#endif
-}
-SWC_HD int top64(uint64_t m) {   // index of the highest set bit, m != 0
-#if defined(__HIP_DEVICE_COMPILE__)
-    return 63 - __clzll((long long)m);
-#else
-    return 63 - __builtin_clzll(m);
-#endif
-}
-
 // R8: records of EIGHT bytes -- the 32-bit record of lz_resolve.h and, in the upper dword, the offset of its literal run in the
 // block (LZ4 literals are byte-aligned in the input, LZ4.swift:364-366): no literal is copied anywhere by the parse, the copy
 // kernel (lz_copy.h) fetches a run from the block itself.  The area then holds header | records | scratch rows.
@@ -166,12 +98,12 @@ SWC_HD int top64(uint64_t m) {   // index of the highest set bit, m != 0
 template <int W, int RM = 0>
 struct Parser {
     static constexpr bool R8 = RM == 1, R4 = RM == 2;
-    Wave<W> w;
+    int lane;
     SWC_AS_GLOBAL uint32_t* anc = nullptr;   // R4: anchors (record index, S) in the order of the records
     uint32_t nanc = 0, max_anc = 0;
     uint64_t s_pred = 0;                     // R4: where the copier's running sum stands (the start of the next sequence by its rule)
     SWC_D void anchor(uint32_t rec, uint64_t S) {
-        if (nanc < max_anc && w.lane == 0) { anc[2u * nanc] = rec; anc[2u * nanc + 1u] = (uint32_t)S; }
+        if (nanc < max_anc && lane == 0) { anc[2u * nanc] = rec; anc[2u * nanc + 1u] = (uint32_t)S; }
         nanc++;
         s_pred = S;
     }
@@ -206,14 +138,14 @@ struct Parser {
 #endif
 
     SWC_D uint64_t chunk_load(uint64_t base) const {   // this lane's 8 bytes of the chunk at `base`
-        const uint64_t a = base + 8 * (uint64_t)w.lane;
+        const uint64_t a = base + 8 * (uint64_t)lane;
         if (a + 8 <= n) return load_u64(in + a);
         uint64_t v = 0;
         for (int j = 0; j < 8; j++) if (a + j < n) v |= (uint64_t)in[a + j] << (8 * j);
         return v;
     }
     SWC_D void chunk_store(uint64_t base, uint64_t v) const {
-        const uint32_t x = (uint32_t)(base + 8 * (uint64_t)w.lane) & (kInWin - 1);
+        const uint32_t x = (uint32_t)(base + 8 * (uint64_t)lane) & (kInWin - 1);
         *(uint64_t*)(iw + x) = v;
         if (x < 16) *(uint64_t*)(iw + kInWin + x) = v;
     }
@@ -240,12 +172,12 @@ struct Parser {
         if (rb_n) {
             constexpr uint32_t kD = R8 ? 2u : 1u;   // dwords per record
             SWC_AS_GLOBAL uint32_t* dst = recs + kD * (nrec - rb_n);
-            for (uint32_t i = (uint32_t)w.lane; i < kD * rb_n; i += (uint32_t)W) dst[i] = rbuf[i];
+            for (uint32_t i = (uint32_t)lane; i < kD * rb_n; i += (uint32_t)W) dst[i] = rbuf[i];
             rb_n = 0;
         }
         if (lb_n) {
             gptr dst = lits + (nlit - lb_n);
-            for (uint32_t i = (uint32_t)w.lane * 8; i < lb_n; i += (uint32_t)W * 8) {
+            for (uint32_t i = (uint32_t)lane * 8; i < lb_n; i += (uint32_t)W * 8) {
                 if (i + 8 <= lb_n) store_u64(dst + i, *(const u64_unaligned*)(lbuf + i));
                 else for (uint32_t j = i; j < lb_n; j++) dst[j] = lbuf[j];
             }
@@ -256,7 +188,7 @@ struct Parser {
     SWC_D void push(uint32_t v, uint64_t from) {   // `from`: where the record's literals lie in the block (R8)
         if (nrec < max_rec) {   // (beyond the workspace: counted only, the job ends with SWC_E_NEED_WORKSPACE)
             if (rb_n >= kRecBuf) flush();
-            if (w.lane == 0) {
+            if (lane == 0) {
                 if (R8) { rbuf[2u * rb_n] = v; rbuf[2u * rb_n + 1u] = (uint32_t)from; }
                 else rbuf[rb_n] = v;
             }
@@ -278,13 +210,13 @@ struct Parser {
         if (keep == 0) return;
         if (RM != 0) { nlit += keep; return; }   // (they stay where they are: the record says where, or the copier's sum does)
         if (keep + lb_n <= kLitStage && from + keep <= iw_hi && from + kInWin >= iw_hi) {
-            for (uint32_t i = (uint32_t)w.lane; i < (uint32_t)keep; i += (uint32_t)W) lbuf[lb_n + i] = iw[(uint32_t)(from + i) & (kInWin - 1)];
+            for (uint32_t i = (uint32_t)lane; i < (uint32_t)keep; i += (uint32_t)W) lbuf[lb_n + i] = iw[(uint32_t)(from + i) & (kInWin - 1)];
             lb_n += (uint32_t)keep;
             nlit += keep;
             return;
         }
         flush();
-        for (uint64_t i = (uint64_t)w.lane * 8; i < keep; i += (uint64_t)W * 8) {
+        for (uint64_t i = (uint64_t)lane * 8; i < keep; i += (uint64_t)W * 8) {
             if (i + 8 <= keep) store_u64(lits + nlit + i, load_u64(in + from + i));
             else for (uint64_t j = i; j < keep; j++) lits[nlit + j] = in[from + j];
         }
@@ -394,11 +326,7 @@ struct Parser {
     SWC_D static uint32_t rd32(const uint8_t* stage, uint32_t a) {   // the four bytes at `a` (aligned LDS reads + a byte shift)
         const uint32_t* st32 = (const uint32_t*)stage;
         const uint32_t lo = st32[stage_slot(a >> 2)], hi = st32[stage_slot((a >> 2) + 1u)];
-#if defined(__HIP_DEVICE_COMPILE__)
-        return __builtin_amdgcn_alignbyte(hi, lo, a & 3u);
-#else
-        return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * (a & 3u)));
-#endif
+        return alignbyte32(hi, lo, a & 3u);
     }
     // One sequence at `ip`, SHORT form only (at most one extension byte per length): literal count, match length, offset,
     // where the literals are and where the next sequence starts; `stop`: the fast path does not take it.
@@ -741,7 +669,7 @@ struct Parser {
             // the last match start of the round: in the last lane that took a sequence
             SIMT_BEGIN(t, N) pb[t] = (uint32_t)t < nv && c_rec[t] != 0; SIMT_END
             const uint64_t m_seq = simt::wave_ballot<N>(pb);
-            const int last = 63 - (int)clz64(m_seq);
+            const int last = simt::top64(m_seq);
             SIMT_BEGIN(t, N) x_lit[t] = (x_out[t] - c_out[t]) + c_lms[t]; SIMT_END
             last_match_start = (int64_t)(pos + simt::wave_read<N>(x_lit, last));
             pos += tot_out;
@@ -776,7 +704,7 @@ template <int W, int RM = 0>
 SWC_D void lz4_parse_job(Job& job, uint8_t* ws, size_t ws_bytes, int lane, uint8_t* stage, uint64_t* prof = nullptr) {
     constexpr bool R8 = RM == 1, R4 = RM == 2;
     Parser<W, RM> ps;
-    ps.w.lane = lane;
+    ps.lane = lane;
     ps.iw = stage + kScratchWin;
     ps.iw_hi = 0;
     ps.iw_next = 0;

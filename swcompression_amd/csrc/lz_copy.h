@@ -69,21 +69,14 @@ SWC_HD uint32_t ld32(const uint8_t* p) { return *(const u32_unaligned*)p; }
 // the low bits of the address): the LDS serves an unaligned ds_read_b32 at about one LANE per cycle (63 cycles for a full
 // wave, tools/micro/lds_bench.hip), an aligned one in 6; unaligned STORES cost a quarter of a cycle per lane and stay.
 // `a` is the byte offset from the (16-byte aligned) base b; up to 7 (rd32u) / 11 (rd64u) bytes behind the value are touched.
-SWC_HD uint32_t alignbyte(uint32_t hi, uint32_t lo, uint32_t a) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_alignbyte(hi, lo, a);
-#else
-    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8u * (a & 3u)));
-#endif
-}
 SWC_HD uint32_t rd32u(const uint8_t* b, uint32_t a) {
     const uint32_t* p = (const uint32_t*)(b + (a & ~3u));
-    return alignbyte(p[1], p[0], a);
+    return alignbyte32(p[1], p[0], a);
 }
 SWC_HD uint64_t rd64u(const uint8_t* b, uint32_t a) {
     const uint32_t* p = (const uint32_t*)(b + (a & ~3u));
     const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
-    return (uint64_t)alignbyte(w1, w0, a) | ((uint64_t)alignbyte(w2, w1, a) << 32);
+    return (uint64_t)alignbyte32(w1, w0, a) | ((uint64_t)alignbyte32(w2, w1, a) << 32);
 }
 SWC_HD void st32(uint8_t* p, uint32_t v) { *(u32_unaligned*)p = v; }
 SWC_HD void st64(uint8_t* p, uint64_t v) { *(u64_unaligned*)p = v; }
@@ -176,24 +169,6 @@ struct Copier {
     P fv;              // flush watermark (a multiple of 16): virtual positions below it have LEFT for `out`
     P landed;          // ... and below this one they have ARRIVED (the flush watermark at the last full wait)
 
-    SWC_D static uint32_t mod_small(uint32_t m, uint32_t d) {   // m % d for m, d < 2^16, d != 0
-#if defined(__HIP_DEVICE_COMPILE__)
-        uint32_t q = (uint32_t)((float)m * __builtin_amdgcn_rcpf((float)d));   // v_rcp_f32: off by at most one, fixed up below
-        uint32_t r = m - q * d;
-        if ((int32_t)r < 0) r += d;
-        if (r >= d) r -= d;
-        return r;
-#else
-        return m % d;
-#endif
-    }
-    SWC_D static void lds_or(uint32_t* p, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-        *p |= v;
-#endif
-    }
     SWC_D static void unpack(uint32_t r, uint32_t& li, uint32_t& le, uint32_t& di) {
         li = r & 127u;
         le = (r >> 7) & 511u;
@@ -671,8 +646,8 @@ struct Copier {
                 if (((pm0 >> t) & 1u) != 0u && flags[t] == 0u) {
                     const uint32_t a = wm[t] - wp;
                     const uint64_t mk = ((1ull << len[t]) - 1ull) << (a & 31u);       // (len <= kLongLen = 32)
-                    lds_or(&l->pmap[a >> 5], (uint32_t)mk);
-                    if ((uint32_t)(mk >> 32) != 0u) lds_or(&l->pmap[(a >> 5) + 1u], (uint32_t)(mk >> 32));
+                    simt::lds_or(&l->pmap[a >> 5], (uint32_t)mk);
+                    if ((uint32_t)(mk >> 32) != 0u) simt::lds_or(&l->pmap[(a >> 5) + 1u], (uint32_t)(mk >> 32));
                 }
             SIMT_END_WAVE
             PT<bool, W> free_;

@@ -135,31 +135,6 @@ struct Resolver {
     uint64_t lit_cap;  // bytes that may be READ from it (allocation size, a multiple of 16)
     uint64_t limit;    // bytes of `out` that exist: min(bytes produced, capacity)
 
-    SWC_D static uint32_t mod_small(uint32_t m, uint32_t d) {   // m % d for m, d < 2^16, d != 0
-#if defined(__HIP_DEVICE_COMPILE__)
-        uint32_t q = (uint32_t)((float)m * __builtin_amdgcn_rcpf((float)d));   // v_rcp_f32: off by at most one, fixed up below
-        uint32_t r = m - q * d;
-        if ((int32_t)r < 0) r += d;
-        if (r >= d) r -= d;
-        return r;
-#else
-        return m % d;
-#endif
-    }
-    SWC_D static void lds_min(uint32_t* p, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-        if (v < *p) *p = v;
-#endif
-    }
-    SWC_D static void lds_or(uint32_t* p, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-        *p |= v;
-#endif
-    }
     // Cells are read while other threads resolve theirs (R3): a reader may see the source index or the value that
     // replaced it -- both are right (16-bit LDS accesses are single accesses; every address is read at most once per hop,
     // so nothing can be cached).  Plain LDS accesses: `volatile` would turn them into flat accesses with a memory wait.
@@ -330,7 +305,7 @@ struct Resolver {
                         for (uint32_t k = 0; k < kRpt; k++) {
                             const uint32_t r = k ? r_nx1[t] : r_nx0[t];
                             const bool big = base + kRpt * (uint32_t)t + k < nrec && ((r >> 7) & 511u) == 0u && (r & 127u) + ((r >> 16) << 7) >= kBigLit;
-                            if (!big) lds_min(&l->nbig, kRpt * (uint32_t)t + k);
+                            if (!big) simt::lds_min(&l->nbig, kRpt * (uint32_t)t + k);
                         }
                     SIMT_END_BARRIER
                     const uint32_t nb = simt::uniform(l->nbig);          // records of the run (>= 1: the first one is big)
@@ -436,9 +411,9 @@ struct Resolver {
                                       : 0xFFFFull;
                     if (take) {
                         // the slots whose first in-span cell I cover, and the flag of my first cell
-                        for (uint32_t q = start == 0 ? 0u : (start + off + 15u) >> 4; q == 0 ? start == 0 : 16u * q - off < end; q++) lds_or(&l->slotw[q], i);
+                        for (uint32_t q = start == 0 ? 0u : (start + off + 15u) >> 4; q == 0 ? start == 0 : 16u * q - off < end; q++) simt::lds_or(&l->slotw[q], i);
                         const uint32_t c0 = start + off;
-                        lds_or(&l->slotw[c0 >> 4], 0x10000u << (c0 & 15u));
+                        simt::lds_or(&l->slotw[c0 >> 4], 0x10000u << (c0 & 15u));
                         if (len > dist) l->overlap = 1;      // (every writer stores the same value)
                         if (i == kRpt * T - 1) { l->ntake = kRpt * (uint32_t)T; l->span = end; l->litspan = lit_end; }
                     } else if (i != 0 && start <= span_max && lit_end - lit <= kLitCap && base + i - 1u < nrec) {

@@ -178,11 +178,7 @@ struct Decoder {
     SWC_HD uint8_t next_byte() {
         const uint32_t k = wk++;   // < 256: ensure_window() ran within the last kSymbolBytes bytes
         if (WAVE == 1) return k < wlim ? in[win_base + k] : (uint8_t)0;
-#if defined(__HIP_DEVICE_COMPILE__)
-        const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)win, __builtin_amdgcn_readfirstlane((int)(k >> 2)));   // (the index is the same in every lane: said so, or the compiler loops over the lanes)
-#else
-        const uint32_t w = win;
-#endif
+        const uint32_t w = simt::lane_read(win, simt::uniform(k >> 2));   // (the index is the same in every lane: said so, or the compiler loops over the lanes)
         return (uint8_t)(w >> (8 * (k & 3u)));
     }
     SWC_HD static bool same(bool c) { return simt::wave_true(c); }
@@ -422,11 +418,7 @@ struct Decoder {
                 // overlapping: every byte is a copy of one of the `distance` bytes before `pos`
                 for (uint32_t i = (uint32_t)lane; i < len; i += WAVE) { last = dst[(int64_t)(i % (uint32_t)distance) - (int64_t)distance]; dst[i] = (uint8_t)last; }
             }
-#if defined(__HIP_DEVICE_COMPILE__)
-            prev_byte = (uint32_t)__builtin_amdgcn_readlane((int)last, __builtin_amdgcn_readfirstlane((int)((len - 1u) % (uint32_t)WAVE)));
-#else
-            prev_byte = last;
-#endif
+            prev_byte = simt::lane_read(last, simt::uniform((len - 1u) % (uint32_t)WAVE));
         }
         overflow = overflow || !fits;
         pos += len;

@@ -297,6 +297,75 @@ SWC_D uint32_t uniform(uint32_t v) {
 #endif
 }
 SWC_D uint64_t uniform(uint64_t v) { return ((uint64_t)uniform((uint32_t)(v >> 32)) << 32) | uniform((uint32_t)v); }
+SWC_HD int top64(uint64_t m) { return 63 - clz64(m); }   // index of the highest set bit, m != 0
+
+// ---- cross-lane steps on plain values, for code that is not written in regions (the wave-per-block bzip2 and LZMA decoders) --
+// The host runs such code ONE LANE AT A TIME (a wave of one): a ballot is the lane's own bit, a read of any lane the lane's own value.
+SWC_D uint64_t lane_ballot(bool p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __ballot(p);
+#else
+    return p ? 1ull : 0ull;
+#endif
+}
+SWC_D uint32_t lane_count(bool p) { return (uint32_t)popc64(lane_ballot(p)); }
+SWC_D uint32_t lane_read(uint32_t v, uint32_t i) {   // value of lane `i` (i the same in every lane)
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)i);
+#else
+    (void)i;
+    return v;
+#endif
+}
+
+// ---- relaxed atomics on an LDS word (workgroup scope) and on a word in memory (agent scope) -------------------------------------
+// The host forms are plain read-modify-writes: the emulation is single-threaded.  The adds return the old value.
+SWC_D void lds_or(uint32_t* p, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#else
+    *p |= v;
+#endif
+}
+SWC_D void lds_min(uint32_t* p, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#else
+    if (v < *p) *p = v;
+#endif
+}
+SWC_D void lds_max(uint32_t* p, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#else
+    if (v > *p) *p = v;
+#endif
+}
+SWC_D uint32_t lds_add(uint32_t* p, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#else
+    const uint32_t old = *p;
+    *p = old + v;
+    return old;
+#endif
+}
+SWC_D void global_or(SWC_AS_GLOBAL uint32_t* p, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    *p |= v;
+#endif
+}
+SWC_D uint32_t global_add(SWC_AS_GLOBAL uint32_t* p, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    const uint32_t old = *p;
+    *p = old + v;
+    return old;
+#endif
+}
 
 }  // namespace simt
 }  // namespace swc

@@ -16,12 +16,17 @@ class Job(C.Structure):
                 ("dict", C.c_void_p), ("dict_len", C.c_uint64)]
 
 
+def compile_lib(out, opt=("-O2", "-g")):
+    """The one recipe of the emulation library; the ASAN tests pass their own optimisation and sanitizer flags."""
+    subprocess.run(["g++"] + list(opt) + ["-std=c++17", "-DSWC_HOST_EMULATION", "-fPIC", "-shared",
+                    "-Wno-unknown-pragmas", "-pthread", "-o", out, os.path.join(_DIR, "emu.cpp")], check=True)
+
+
 def build(force=False):
     srcs = [os.path.join(_DIR, "emu.cpp")] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
     if not force and os.path.exists(_LIB) and all(os.path.getmtime(_LIB) >= os.path.getmtime(s) for s in srcs):
         return
-    subprocess.run(["g++", "-O2", "-g", "-std=c++17", "-DSWC_HOST_EMULATION", "-fPIC", "-shared",
-                    "-Wno-unknown-pragmas", "-pthread", "-o", _LIB, os.path.join(_DIR, "emu.cpp")], check=True)
+    compile_lib(_LIB)
 
 
 build()
@@ -33,9 +38,9 @@ def set_order(order):
     lib.emu_set_order(C.c_int(order))
 
 
-def run_batch(fn_name, inputs, caps, aux=None, dicts=None, extra=None, fn_args=(), dict_ptr_values=None, misalign=0):
+def run_batch(fn_name, inputs, caps, aux=None, dicts=None, extra=None, fn_args=(), dict_ptr_values=None, misalign=0, lib=None):
     """inputs: list[bytes]; caps: list[int].  Returns list of (status, out_bytes, in_consumed, out_len).
-    misalign: the output buffers start that many bytes past a 16-byte boundary."""
+    misalign: the output buffers start that many bytes past a 16-byte boundary.  lib: another build of the library (ASAN)."""
     n = len(inputs)
     jobs = (Job * n)()
     keep = []
@@ -59,7 +64,7 @@ def run_batch(fn_name, inputs, caps, aux=None, dicts=None, extra=None, fn_args=(
             jobs[i].dict_len = extra[i]
         if dict_ptr_values is not None:
             jobs[i].dict = dict_ptr_values[i]
-    getattr(lib, fn_name)(jobs, C.c_size_t(n), *fn_args)
+    getattr(lib or globals()["lib"], fn_name)(jobs, C.c_size_t(n), *fn_args)
     res = []
     for i in range(n):
         ib, ob, o0 = keep[i] if dicts is None else [k for k in keep if isinstance(k, tuple)][i]

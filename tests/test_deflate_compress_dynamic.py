@@ -5,7 +5,7 @@ The contract: the same parse as the static path, one block per unit, the block d
 than the static one and stored where that is not larger than the better of the two -- so the stream is never larger than the
 static path's, and where no block is dynamic its bytes ARE the static path's.  Every header keeps to the form zlib writes
 (complete codes, 15 / 15 / 7 bits at most, each table run-length coded on its own).
-CPU tier: the kernel source on the host emulation (tests/host_emu/emu_deflate_dynamic.cpp)."""
+CPU tier: the kernel source on the host emulation (tests/host_emu/emu.cpp, through tests/_emu_dynamic.py)."""
 import ctypes as C
 import json
 import os
@@ -274,8 +274,8 @@ def test_dynamic_emulation_is_asan_clean(tmp_path):
     asan = subprocess.run(["gcc", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
     if not asan or not os.path.isabs(asan) or shutil.which("g++") is None:
         pytest.skip("no AddressSanitizer runtime")
-    lib = str(tmp_path / "libswc_emu_deflate_dynamic_asan.so")
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address", "-fno-omit-frame-pointer"] + D.FLAGS + ["-o", lib, D.SRC], check=True)
+    lib = str(tmp_path / "libswc_emu_asan.so")
+    E.compile_lib(lib, opt=("-O1", "-g", "-fsanitize=address", "-fno-omit-frame-pointer"))
     child = tmp_path / "child.py"
     child.write_text(ASAN_CHILD)
     env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0",

@@ -8,6 +8,8 @@ import sys
 
 import pytest
 
+import _emu
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -16,8 +18,7 @@ def test_emulated_kernels_are_asan_clean(tmp_path):
     if not asan or not os.path.isabs(asan) or shutil.which("g++") is None:
         pytest.skip("no AddressSanitizer runtime")
     lib = str(tmp_path / "libswc_emu_asan.so")
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address", "-fno-omit-frame-pointer", "-std=c++17", "-DSWC_HOST_EMULATION",
-                    "-fPIC", "-shared", "-Wno-unknown-pragmas", "-pthread", "-o", lib, os.path.join(HERE, "host_emu", "emu.cpp")], check=True)
+    _emu.compile_lib(lib, opt=("-O1", "-g", "-fsanitize=address", "-fno-omit-frame-pointer"))
     env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0")
     p = subprocess.run([sys.executable, os.path.join(HERE, "_asan_child.py"), lib], capture_output=True, text=True, env=env, timeout=600)
     assert p.returncode == 0 and "asan-clean" in p.stdout, (p.stdout[-2000:], p.stderr[-4000:])
