@@ -67,6 +67,20 @@ for kind, size in (("text", 300000), ("mix", 200000), ("rep", 100000), ("zero", 
             n += 2
     lib.emu_set_deflate_team(0)
     n += 2
+# Deflate streams built code by code (_deflate_build.py): the deep code sets make the checked step and the subtable spill read the
+# workspace; the error cases stop inside rounds the fast path has staged beyond
+import _deflate_build  # noqa: E402
+for team in (0, 1):
+    lib.emu_set_deflate_team(team)
+    for c in _deflate_build.directed_cases():
+        if c.status == 0:
+            assert run("emu_inflate_sync", c.stream, c.plain)[0], ("built", c.name, team)
+            assert not run("emu_inflate_sync", c.stream[:len(c.stream) * 2 // 3], c.plain)[0], ("built, truncated", c.name, team)
+            n += 2
+        else:
+            assert run("emu_inflate_sync", c.stream, b"", cap=80000)[1] == c.status, ("built", c.name, team)
+            n += 1
+lib.emu_set_deflate_team(0)
 # LZMA2 in both model layouts (all literal coders in LDS / LDS as a cache of four), whole and truncated
 import lzma as _lzma
 lib.emu_lzma_mode.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int]

@@ -15,6 +15,7 @@ import zlib
 import numpy as np
 import pytest
 
+import _deflate_build as B
 import _oracle as O
 import _streams as S
 import swcompression_amd as swc
@@ -306,3 +307,106 @@ def test_phase1_team_and_single_wavefront_write_the_same():
     finally:
         lib.swc_set_tuning(b"deflate_team", 1)
         O.lib.refcpu_set_max_output(1 << 30)
+
+
+# ------------------------------------------------------------------------- streams built code by code (tests/_deflate_build.py)
+@pytest.fixture(scope="module")
+def directed():
+    """The directed set and the oracle's word on it, computed once and never changed; each case held to the KIND of result it was
+    built for, so that a builder mistake which turns a corner into an early error fails here."""
+    cases = B.directed_cases()
+    exp = [O.deflate(c.stream) for c in cases]
+    for c, e in zip(cases, exp):
+        if c.status == 0:
+            assert e == (0, c.plain, c.body_len), c.name
+        else:
+            assert e[0] == c.status, "%s: oracle status %d, built for %d" % (c.name, e[0], c.status)
+    return cases, exp
+
+
+def _directed_batch(cases, exp, caps, label, tile=1):
+    b = DeviceBatch("deflate", [c.stream for c in cases], caps, tile=tile)
+    b.launch(sync=True)
+    r = b.results()
+    for i, (c, e) in enumerate(zip(cases, exp)):
+        assert int(r["status"][i]) == e[0], "%s, %s: status %d, oracle %d" % (label, c.name, int(r["status"][i]), e[0])
+        if e[0] == 0:
+            assert int(r["out_len"][i]) == len(e[1]) and int(r["in_consumed"][i]) == e[2], "%s, %s: out_len / in_consumed" % (label, c.name)
+            assert b.output(i, len(e[1])) == e[1], "%s, %s: bytes differ" % (label, c.name)
+    return b, r
+
+
+def test_built_streams_directed(directed, lz_copy_kernel):
+    """What zlib never writes: the last 262 distances, 258 as 284 + 31, pairs of 48 bits across sub-chunk and round ends, code sets
+    that spill the LDS subtables, code-length runs across the literal / distance boundary, HCLEN 4 and 19, one or no distance code,
+    hundreds of blocks in a sub-chunk, errors behind committed rounds -- under the three forms of phase 1 (the copy kernel is the
+    fixture's), at exact capacity and with five bytes to spare."""
+    from swcompression_amd import _lib
+    lib = _lib.load()
+    cases, exp = directed
+    try:
+        for team in (1, 0, -1):
+            assert lib.swc_set_tuning(b"deflate_team", team) == 0
+            for spare in (0, 5):
+                _directed_batch(cases, exp, [max(len(e[1]), 1) + spare for e in exp], "team %d, %s, capacity + %d" % (team, lz_copy_kernel, spare))
+    finally:
+        lib.swc_set_tuning(b"deflate_team", 1)
+
+
+def test_built_streams_300_copies_in_one_launch(directed):
+    """300 copies of the directed set in one launch: one wavefront per stream by the library's own choice, each wavefront's LDS
+    (tables, subtables, staged rounds) used by several streams one after the other.  The first copy equals the oracle; every other
+    copy equals the first -- status, lengths, and (for the streams that decode) bytes, compared on the device."""
+    import torch
+    cases, exp = directed
+    tile, nd = 300, len(cases)
+    b, r = _directed_batch(cases, exp, [max(len(e[1]), 1) for e in exp], "300 copies", tile=tile)
+    assert b.n == tile * nd
+    ok = np.array([e[0] == 0 for e in exp])
+    for field in ("status", "in_consumed", "out_len"):   # (the lengths are part of the contract for the streams that decode)
+        got = r[field].reshape(tile, nd)[:, ok | (field == "status")]
+        assert (got == got[0]).all(), "%s differs in copies %s" % (field, sorted(set(np.nonzero(got != got[0])[0]))[:10])
+    span = int(b._out_off[nd])
+    assert all(int(b._out_off[t * nd + k]) == t * span + int(b._out_off[k]) for t in (1, tile - 1) for k in range(nd))
+    for k, e in enumerate(exp):
+        if e[0] == 0 and len(e[1]):
+            v = torch.as_strided(b.d_out, (tile, len(e[1])), (span, 1), int(b._out_off[k]))
+            same = (v == v[0]).all(dim=1)
+            assert bool(same.all()), "%s: copies %s differ from the first" % (cases[k].name, torch.nonzero(~same).flatten()[:10].tolist())
+
+
+def test_built_streams_single_shot(directed):
+    """The small-launch path (inflate_team.hip: a team of wavefronts on one stream) on every directed stream."""
+    cases, exp = directed
+    for c, (st, out, cons) in zip(cases, exp):
+        if st == 0:
+            assert swc.Deflate.decompress_consumed(c.stream) == (out, cons), c.name
+        else:
+            with pytest.raises(swc.SWCError) as ei:
+                swc.Deflate.decompress(c.stream)
+            assert ei.value.status == st, c.name
+
+
+def test_built_streams_as_gzip_members(directed):
+    """The container path of the headline (swc.unarchive_many: device CRC-32, ISIZE) on outputs made of 32,768-distance matches, of
+    deep code sets and of 65,535-byte stored blocks; one flipped CRC."""
+    import struct
+    cases, _ = directed
+    names = ["every-symbol-at-both-extremes-dynamic", "length-258-as-284-plus-31", "distance-32768-at-output-32768", "distance-32768-at-output-65543",
+             "pairs-of-48-bits-over-several-rounds", "deep-literal-set-256-long-codes", "deep-distance-set-15-bit-codes", "deep-sets-on-both-sides",
+             "286-codes-of-11-bits", "same-symbols-three-blocks-three-deep-sets", "one-distance-code-of-one-bit", "200-empty-fixed-blocks-then-data",
+             "stored-blocks-at-each-bit-alignment", "stored-blocks-of-65535-bytes"]
+    by_name = {c.name: c for c in cases}
+    members = []
+    for n in names:
+        c = by_name[n]
+        members.append(b"\x1f\x8b\x08\x00" + b"\0\0\0\0" + b"\x00\xff" + c.stream[:c.body_len] + struct.pack("<II", zlib.crc32(c.plain) & 0xFFFFFFFF, len(c.plain) & 0xFFFFFFFF))
+    bad = bytearray(members[4])
+    bad[-8] ^= 1
+    members.append(bytes(bad))
+    want = [O.gzip_unarchive(m) for m in members]
+    assert [w[0] for w in want] == [0] * len(names) + [605] and [w[1] for w in want] == [by_name[n].plain for n in names] + [by_name[names[4]].plain]
+    got = swc.unarchive_many("gzip", members)
+    for n, g, w in zip(names + ["a flipped CRC"], got, want):
+        assert g[0] == w[0], "%s: status %d, oracle %d" % (n, g[0], w[0])
+        assert g[1] == w[1], "%s: bytes differ" % n

@@ -5,7 +5,8 @@ blocks are assembled sequence by sequence (LZ4.swift:341-412) from random litera
 that sit on and around every boundary of the two kernels' record formats (literal runs of 14 / 15 / 16 / 269 / 270 and of
 kilobytes, match lengths of 18 / 19 / 20 / 273 / 274 and of tens of kilobytes, offsets of 1 .. 65,535 including the ones that
 reach exactly to the start of the output), and the Deflate streams come from zlib over plain text that is itself a random
-splice of payload classes and copies of earlier stretches at every distance up to the window.  Every stream is decoded by
+splice of payload classes and copies of earlier stretches at every distance up to the window -- and, since zlib is a narrow
+encoder too, from a builder of their own (_deflate_build.py) that writes them code by code.  Every stream is decoded by
 the oracle; the engine must return the oracle's status and -- for status 0 -- its bytes, consumed input and length; damaged
 copies (bit flips, truncations, garbage tails) must return the oracle's status.  Each round runs once with the library's
 choice of phase-2 kernel and once with the wave kernel forced.
@@ -17,6 +18,7 @@ import random
 
 import pytest
 
+import _deflate_build as B
 import _oracle as O
 import _soak as K
 from swcompression_amd.batch import DeviceBatch
@@ -86,6 +88,41 @@ def test_deflate_streams_over_spliced_text(seed):
         lib = _lib.load()
         try:
             for team in (1, 0, -1):   # phase 1: the library's choice (launches of up to 256 streams: a team of wavefronts per stream), one wavefront per stream, teams forced
+                assert lib.swc_set_tuning(b"deflate_team", team) == 0
+                _both_kernels(lambda label: _check("deflate", [streams[i] for i in keep], [exp[i] for i in keep], caps, "seed %d, team %d, %s" % (seed, team, label)))
+        finally:
+            lib.swc_set_tuning(b"deflate_team", 1)
+    finally:
+        O.lib.refcpu_set_max_output(1 << 30)
+
+
+BUILT_SEED = 0xB111D0DE
+BUILT_STREAMS, BUILT_DAMAGED = 120, 100
+
+
+@pytest.mark.parametrize("seed", range(ROUNDS))
+def test_deflate_streams_built_code_by_code(seed):
+    """Streams no encoder writes (tests/_deflate_build.py: all three block types, random complete code sets up to 15 bits, header
+    runs across the literal / distance boundary, every distance up to 32,768, 258 as 284 + 31, blocks of a few tokens) and damaged
+    copies of them.  Built once per seed, then the three forms of phase 1 times both copy kernels."""
+    rnd = random.Random(BUILT_SEED + seed)
+    O.lib.refcpu_set_max_output(1 << 24)
+    try:
+        streams = []
+        for i in range(BUILT_STREAMS):
+            # (four streams of 200,000 bytes per seed, none of them in the tiny-block style: building in Python, not decoding, is what they cost)
+            z, p, body = B.random_stream(rnd, 200000 if i < 4 else rnd.choice([0, 1, 9, 300, 4000, 65536, 70000]), (i + seed) % (3 if i < 4 else 4))
+            assert O.deflate(z) == (0, p, body), "the builder and the oracle disagree on a stream it built (seed %d, stream %d)" % (seed, i)
+            streams.append(z)
+        streams += [K.damage(rnd, streams[rnd.randrange(BUILT_STREAMS)]) for _ in range(BUILT_DAMAGED)]
+        exp = [O.deflate(z) for z in streams]
+        keep = [i for i, e in enumerate(exp) if i < BUILT_STREAMS or e[0] != 901]   # (no undamaged stream is ever left out)
+        assert len(streams) - len(keep) <= BUILT_DAMAGED // 10, "%d damaged copies beyond the oracle's output cap" % (len(streams) - len(keep))
+        caps = [max(len(exp[i][1]), 1) + rnd.choice([0, 0, 0, 5]) for i in keep]
+        from swcompression_amd import _lib
+        lib = _lib.load()
+        try:
+            for team in (1, 0, -1):
                 assert lib.swc_set_tuning(b"deflate_team", team) == 0
                 _both_kernels(lambda label: _check("deflate", [streams[i] for i in keep], [exp[i] for i in keep], caps, "seed %d, team %d, %s" % (seed, team, label)))
         finally:

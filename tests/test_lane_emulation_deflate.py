@@ -6,6 +6,7 @@ import random
 
 import pytest
 
+import _deflate_build as B
 import _emu as E
 import _oracle as O
 import _streams as S
@@ -185,3 +186,45 @@ def test_the_team_adopts_its_helpers_rounds():
         assert (st, out, cons) == (0, p, len(z))
         got = E.lib.emu_team_adopted(1)
         assert got >= least and (least or got == 0), (kind, got)
+
+
+def _directed_expectations():
+    """The oracle on the directed set of _deflate_build.py, each case held to the KIND of result it was built for: a builder
+    mistake that turns a corner into an early error must fail here, not pass as "the engine agrees with the oracle"."""
+    cases = B.directed_cases()
+    exp = [O.deflate(c.stream) for c in cases]
+    for c, e in zip(cases, exp):
+        if c.status == 0:
+            assert e == (0, c.plain, c.body_len), c.name
+        else:
+            assert e[0] == c.status, "%s: oracle status %d, built for %d" % (c.name, e[0], c.status)
+    return cases, exp
+
+
+def _check_directed(cases, exp, res, label=""):
+    for c, e, r in zip(cases, exp, res):
+        st, out, cons, n = r
+        assert st == e[0], "%s%s: status %d, oracle %d" % (label, c.name, st, e[0])
+        if e[0] == 0:
+            assert out == e[1] and cons == e[2] and n == len(e[1]), "%s%s: bytes / in_consumed / out_len" % (label, c.name)
+
+
+def test_built_streams_directed(inflate):
+    """What zlib never writes (tests/_deflate_build.py: directed_cases): the last 262 distances, 258 as 284 + 31, pairs of 48 bits
+    across sub-chunk and round ends, code sets that spill the LDS subtables, code-length runs across the literal / distance
+    boundary, HCLEN 4 and 19, one or no distance code, hundreds of blocks in a sub-chunk, errors behind committed rounds."""
+    cases, exp = _directed_expectations()
+    ins = [c.stream for c in cases]
+    _check_directed(cases, exp, inflate(ins, [max(len(e[1]), 1) for e in exp]))
+    _check_directed(cases, exp, inflate(ins, [max(len(e[1]), 1) + 5 for e in exp]), "capacity + 5, ")
+
+
+@pytest.mark.parametrize("order,misalign", [(1, 0), (2, 7), (1, 15)])
+def test_built_streams_directed_thread_order_and_output_alignment(order, misalign):
+    cases, exp = _directed_expectations()
+    E.set_order(order)
+    try:
+        res = E.inflate([c.stream for c in cases], [max(len(e[1]), 1) for e in exp], misalign=misalign)
+    finally:
+        E.set_order(0)
+    _check_directed(cases, exp, res, "order %d, misalignment %d, " % (order, misalign))

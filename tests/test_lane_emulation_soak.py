@@ -6,6 +6,7 @@ import random
 
 import pytest
 
+import _deflate_build as B
 import _emu as E
 import _oracle as O
 import _soak as K
@@ -65,6 +66,38 @@ def test_deflate_streams_over_spliced_text(seed, bounded_oracle):
         for team in (0, 1):         # one wavefront per stream / a team of wavefronts
             E.lib.emu_set_deflate_team(team)
             for copier in (1, 2, 0):    # the Deflate window, the LZ4 window, the workgroup resolver
+                E.lib.emu_set_copier(copier)
+                _compare(E.inflate(ins, caps, misalign=seed % 16), want, ins, "seed %d, team %d, copier %d" % (seed, team, copier))
+    finally:
+        E.lib.emu_set_deflate_team(0)
+
+
+BUILT_STREAMS, BUILT_DAMAGED = 48, 48
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_deflate_streams_built_code_by_code(seed, bounded_oracle):
+    """Streams of tests/_deflate_build.py (every block type, random complete code sets up to 15 bits, header runs across the literal /
+    distance boundary, every distance up to 32,768, 258 as 284 + 31, tiny blocks) and damaged copies: each seed's set is built once
+    and goes through both forms of phase 1 and the three copiers."""
+    rnd = random.Random(0xEB111D + seed)
+    streams = []
+    for i in range(BUILT_STREAMS):
+        # (two streams of 200,000 bytes per seed, none of them in the tiny-block style: building in Python, not decoding, is what they cost)
+        z, p, body = B.random_stream(rnd, 200000 if i < 2 else rnd.choice([0, 1, 9, 300, 4000, 65536, 70000]), (i + seed) % (3 if i < 2 else 4))
+        assert O.deflate(z) == (0, p, body), "the builder and the oracle disagree (seed %d, stream %d)" % (seed, i)
+        streams.append(z)
+    streams += [K.damage(rnd, streams[rnd.randrange(BUILT_STREAMS)]) for _ in range(BUILT_DAMAGED)]
+    exp = [O.deflate(z) for z in streams]
+    keep = [i for i, e in enumerate(exp) if i < BUILT_STREAMS or e[0] != 901]   # (no undamaged stream is ever left out)
+    assert len(streams) - len(keep) <= BUILT_DAMAGED // 10, "%d damaged copies beyond the oracle's output cap" % (len(streams) - len(keep))
+    ins, want = [streams[i] for i in keep], [exp[i] for i in keep]
+    caps = [max(len(e[1]), 1) + rnd.choice([0, 0, 0, 5]) for e in want]
+    E.set_order(seed % 3)
+    try:
+        for team in (0, 1):
+            E.lib.emu_set_deflate_team(team)
+            for copier in (1, 2, 0):
                 E.lib.emu_set_copier(copier)
                 _compare(E.inflate(ins, caps, misalign=seed % 16), want, ins, "seed %d, team %d, copier %d" % (seed, team, copier))
     finally:
