@@ -178,6 +178,29 @@ int swc_gzip_archive(const uint8_t* data, size_t len, const uint8_t* comment, si
 int swc_gzip_archive_dynamic(const uint8_t* data, size_t len, const uint8_t* comment, size_t comment_len, const uint8_t* file_name,
                              size_t file_name_len, int write_header_crc, int is_text_file, int os_type, int has_mtime, int64_t mtime,
                              const swc_gzip_extra_field* extra, size_t n_extra, uint8_t** out, size_t* out_len);
+/* BGZF writer (an extension: the reference writes no BGZF; SAM/BAM specification 4.1).  The input is cut into chunks of
+ * block_size bytes (1..65280; 0 = 65280 = 0xFF00, what bgzip cuts; more: SWC_E_INVALID_ARGUMENT), every chunk becomes one gzip
+ * member -- 1f 8b 08 04, MTIME 0, XFL 0, OS 255, the extra field 'BC' with BSIZE = member size - 1, ONE final Deflate block as
+ * SWC_CODEC_DEFLATE_COMPRESS (dynamic != 0: SWC_CODEC_DEFLATE_COMPRESS_DYNAMIC) writes it, CRC-32 and ISIZE of the chunk -- and
+ * the 28-byte end-of-file member closes the file, for empty input too.  All members are compressed in one launch, summed, and packed
+ * one behind the other on the device (csrc/bgzf_pack.h).  The result decodes in one launch through swc_gzip_multi_unarchive /
+ * swc_index_blocks kind 1.
+ *   swc_bgzf_bound            the largest file `len` bytes can become: len + 31 * ceil(len / block_size) + 28 (0: bad block_size)
+ *   swc_bgzf_workspace_bytes  device scratch of swc_batch_bgzf_archive for that input (job lists, offsets, a slot per member)
+ *   swc_batch_bgzf_archive    device-resident: src, dst, total (one uint64), member_sizes (n + 1 uint64 -- the size of every member,
+ *                             the end-of-file member last -- or NULL) and workspace are DEVICE pointers.  Returns when its kernels
+ *                             have run (the status is the outcome of the device work, whatever opts->synchronize says): the first
+ *                             compress error by member index, SWC_E_CAPACITY with the needed length in *total and no byte written
+ *                             when the file does not fit dst_cap, SWC_E_NEED_WORKSPACE when the workspace is too small.
+ *   swc_bgzf_archive          host buffers; *sizes (swc_free, `sizes` may be NULL) = the size of every member incl. the end-of-file
+ *                             member.  The input is staged once and packed in rounds of 16,384 members (1 GiB), so the device
+ *                             scratch stays near 1.2 GB whatever the input; every round lands at its place in the result. */
+size_t swc_bgzf_bound(size_t len, size_t block_size);
+size_t swc_bgzf_workspace_bytes(size_t len, size_t block_size);
+int swc_batch_bgzf_archive(const uint8_t* src, uint64_t len, uint64_t block_size, int dynamic, uint8_t* dst, uint64_t dst_cap,
+                           uint64_t* total, uint64_t* member_sizes, void* workspace, size_t workspace_bytes, const swc_batch_opts* opts);
+int swc_bgzf_archive(const uint8_t* data, size_t len, size_t block_size, int dynamic, uint8_t** out, size_t* out_len, size_t** sizes,
+                     size_t* n_members);
 /* BZip2.compress(data:blockSize:) BZip2+Compress.swift:40-74 (BZip2.compress(data:) :19-21 = block_size 1).  block_size 1..9 =
  * BlockSize.one ... .nine (else SWC_E_INVALID_ARGUMENT); the input is cut into blocks of block_size x 80,000 bytes as the
  * reference cuts it (:46), all blocks are compressed on the device together: initial run-length coding, Burrows-Wheeler
@@ -330,7 +353,9 @@ const char* swc_version(void);
  *   "bzip2_team_walk" = 1 | 0 | 2   process-wide: BZip2 launches run stage 3 -- the inverse Burrows-Wheeler walk, the lay-out,
  *                               the RLE1 undo -- as kernels of their own that walk out of the XCDs' L2 (csrc/bzip2_team.h)
  *                               unless the launch is tiny (1, default), never (0: one wavefront takes a block through all
- *                               stages), or always (2). */
+ *                               stages), or always (2);
+ *   "bgzf_round_members" = 1..16384   process-wide, for tests: members per round of swc_bgzf_archive (default 16384); the file is
+ *                               the same bytes whatever the round size. */
 int swc_set_tuning(const char* key, int value);
 /* Profile builds of the library (-DSWC_PROFILE) only: a device buffer of 32 x uint64 per job of the next Deflate
  * launches that the kernels fill with cycle counts per stage (tools/exp_profile.py).  NULL switches it off.  A no-op in
@@ -339,7 +364,7 @@ int swc_set_profile_buffer(void* device_ptr);
 /* With "phase_timing" on: durations (ms) of the kernels of the calling thread's last batch launch, in launch order --
  * Deflate: entropy decode, LZ77 resolve; LZ4: dictionary-block kernel, parse, resolve; BZip2: block kernel (Huffman + MTF,
  * counting sort, walk), with "bzip2_team_walk" the team walk and the team finish, serial fallback, block CRC; LZMA / LZMA2:
- * the one kernel.  Returns the number of values written (0 if none or if `cap` is too small; at most 5). */
+ * the one kernel; swc_batch_bgzf_archive: compress, CRC-32 of the chunks, offsets + pack.  Returns the number of values written (0 if none or if `cap` is too small; at most 5). */
 int swc_last_phase_ms(float* ms, int cap);
 
 /* Process-wide launch statistics of the host framing layer (monotonic, for tests and tuning): "launches" = batched

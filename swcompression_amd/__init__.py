@@ -260,6 +260,27 @@ class GzipArchive:
             _raise(st, res)
         return res
 
+    @staticmethod
+    def bgzf_archive(data, block_size=65280, dynamic=False, sizes=False):
+        """BGZF (blocked gzip, SAM/BAM specification 4.1; an extension -- the reference writes none): `data` cut into chunks of
+        block_size bytes (1..65280), one gzip member with the 'BC' field each, the 28-byte end-of-file member behind them.  All
+        members are compressed, summed and packed on the device (swc_bgzf_archive); multi_unarchive decodes the file in one
+        launch.  sizes=True: (file, [size of every member, the end-of-file member last])."""
+        if not 1 <= int(block_size) <= 65280:
+            _raise(903)
+        lib = _lib.load()
+        data = bytes(data)
+        out = C.POINTER(C.c_uint8)()
+        n = C.c_size_t()
+        szs = C.POINTER(C.c_size_t)()
+        cnt = C.c_size_t()
+        st = lib.swc_bgzf_archive(data, len(data), int(block_size), int(bool(dynamic)), C.byref(out), C.byref(n), C.byref(szs), C.byref(cnt))
+        members = _take_sizes(szs, cnt.value)
+        res = _take(out, n.value)
+        if st:
+            _raise(st)
+        return (res, members) if sizes else res
+
 
 class ZlibArchive:
     @staticmethod

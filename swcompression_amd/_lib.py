@@ -83,6 +83,11 @@ def load():
     for n in ("swc_gzip_archive", "swc_gzip_archive_dynamic"):
         sig(n, I, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, I, I, I, I, C.c_int64,
             C.c_void_p, C.c_size_t, u8pp, szp)
+    sig("swc_bgzf_bound", C.c_size_t, C.c_size_t, C.c_size_t)
+    sig("swc_bgzf_workspace_bytes", C.c_size_t, C.c_size_t, C.c_size_t)
+    sig("swc_batch_bgzf_archive", I, C.c_void_p, C.c_uint64, C.c_uint64, I, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+        C.c_void_p, C.c_size_t, C.POINTER(SwcBatchOpts))
+    sig("swc_bgzf_archive", I, C.c_char_p, C.c_size_t, C.c_size_t, I, u8pp, szp, szpp, szp)
     sig("swc_lz4_compress", I, C.c_char_p, C.c_size_t, I, I, I, I, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int64, u8pp, szp)
     sig("swc_zip_get_entries_data", I, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t)
     sig("swc_stat", C.c_longlong, C.c_char_p)

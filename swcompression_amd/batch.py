@@ -162,3 +162,30 @@ class DeviceBatch:
         ln = int(min(r["out_len"][i], r["out_cap"][i])) if n is None else n
         o = int(self._out_off[i])
         return self.d_out[o:o + ln].cpu().numpy().tobytes()
+
+
+def bgzf_workspace_bytes(n_bytes, block_size=65280):
+    return _lib.load().swc_bgzf_workspace_bytes(int(n_bytes), int(block_size))
+
+
+def bgzf_archive(src, dst, block_size=65280, dynamic=False, workspace=None, dst_cap=None, sizes=True):
+    """The device-resident BGZF writer (`swc_batch_bgzf_archive`): `src` and `dst` are torch uint8 tensors in HBM, `workspace` one
+    of bgzf_workspace_bytes(src.numel(), block_size) bytes (allocated here when None), dst_cap the room in `dst` (default: all of
+    it).  Returns (status, total, member_sizes): the swc_status of the call, the length of the file -- the length NEEDED for
+    SWC_E_CAPACITY (901), when nothing has been written -- and, with sizes=True, a numpy uint64 array of the size of every member,
+    the end-of-file member last."""
+    import torch
+    lib = _lib.load()
+    n = int(src.numel())
+    block_size = int(block_size) or 65280
+    members = (n + block_size - 1) // block_size
+    if workspace is None:
+        workspace = torch.empty(max(bgzf_workspace_bytes(n, block_size), 16), dtype=torch.uint8, device=src.device)
+    meta = torch.zeros(members + 2, dtype=torch.int64, device=src.device)
+    dev = src.device
+    opts = _lib.SwcBatchOpts(dev.index if dev.index is not None else -1, torch.cuda.current_stream(dev).cuda_stream, 1, 0)
+    st = lib.swc_batch_bgzf_archive(src.data_ptr(), n, int(block_size), int(bool(dynamic)), dst.data_ptr(),
+                                    int(dst.numel()) if dst_cap is None else int(dst_cap), meta.data_ptr(),
+                                    meta.data_ptr() + 8 if sizes else None, workspace.data_ptr(), int(workspace.numel()), C.byref(opts))
+    host = meta.cpu().numpy().view(np.uint64)
+    return st, int(host[0]), (host[1:] if sizes else None)

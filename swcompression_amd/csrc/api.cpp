@@ -16,6 +16,7 @@
 #include <string.h>
 #include "host_util.h"
 #include "launch.h"
+#include "framing.h"
 
 static_assert(sizeof(swc_job) == sizeof(swc::Job), "swc_job and swc::Job must have the same layout");
 static_assert(offsetof(swc_job, status) == offsetof(swc::Job, status), "layout");
@@ -442,6 +443,7 @@ int swc_set_tuning(const char* key, int value) try {
     if (!strcmp(key, "deflate_team") && value >= -1 && value <= 1) { set_deflate_team(value); return SWC_OK; }
     if (!strcmp(key, "bzip2_hot_cxx") && (value == 0 || value == 1)) { set_bzip2_hot_cxx(value); return SWC_OK; }
     if (!strcmp(key, "bzip2_team_walk") && value >= 0 && value <= 2) { set_bzip2_team_walk(value); return SWC_OK; }
+    if (!strcmp(key, "bgzf_round_members") && value >= 1 && value <= 16384) { set_bgzf_round_members(value); return SWC_OK; }
     if (!strcmp(key, "pinned_keep_mib") && value >= 0) { g_pinned_keep = (size_t)value << 20; return SWC_OK; }
     if (!strcmp(key, "result_cache_mib") && value >= 0) { g_result_cache = (size_t)value << 20; return SWC_OK; }
     if (!strcmp(key, "pool_keep_mib") && value >= 0) {   // applies to the current device at once, to the others when they are first used

@@ -14,6 +14,7 @@ int gzip_parse_header(const uint8_t* d, size_t n, size_t& pos, GzipHeaderInfo* i
 int gzip_member_prepare(const uint8_t* d, size_t n, size_t pos, HostUnit& u);
 int gzip_member_finish(const uint8_t* d, size_t n, size_t data_pos, const HostUnit& u, size_t& next_pos, bool& crc_error);
 int zlib_parse_header(const uint8_t* d, size_t n, size_t& pos);
+void set_bgzf_round_members(int v);   // "bgzf_round_members" (swc_set_tuning): members per round of swc_bgzf_archive
 // many-archive batching helpers (framing_many.cpp)
 struct Lz4Plan {
     struct Impl;

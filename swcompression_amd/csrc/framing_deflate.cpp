@@ -10,8 +10,11 @@
 #include <new>
 #include <algorithm>
 #include <vector>
+#include <atomic>
 #include "host_util.h"
 #include "framing.h"
+#include "launch.h"
+#include "bgzf_pack.h"
 
 namespace swc {
 
@@ -489,6 +492,107 @@ int swc_zlib_archive(const uint8_t* data, size_t len, uint8_t** out, size_t* out
 }
 int swc_zlib_archive_dynamic(const uint8_t* data, size_t len, uint8_t** out, size_t* out_len) {
     return zlib_archive_impl(SWC_CODEC_DEFLATE_COMPRESS_DYNAMIC, data, len, out, out_len);
+}
+
+// ---- BGZF writer (an extension: the reference has none; csrc/bgzf_pack.h) ----------------------------------------
+}  // extern "C"
+namespace swc {
+static std::atomic<size_t> g_bgzf_round{16384};   // members per round of the host entry: 1 GiB of input at the default block size
+void set_bgzf_round_members(int v) { g_bgzf_round = (size_t)v; }
+static bool bgzf_block_size(uint64_t& bs) {
+    if (bs == 0) bs = bgzf::kMaxBlock;
+    return bs <= bgzf::kMaxBlock;
+}
+// The device work of one call on `stream`, and its outcome (the call waits for it: the status is what it returns).
+static int bgzf_run(const uint8_t* src, uint64_t len, uint64_t bs, int dynamic, uint8_t* dst, uint64_t dst_cap, uint64_t* total,
+                    uint64_t* sizes, void* workspace, size_t workspace_bytes, bool eof, hipStream_t stream, uint64_t* total_host) {
+    const bgzf::Plan p = bgzf::plan(len, bs);
+    uint8_t* ws = reinterpret_cast<uint8_t*>(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
+    if (!workspace || workspace_bytes < p.bytes + (size_t)(ws - static_cast<uint8_t*>(workspace))) return SWC_E_NEED_WORKSPACE;
+    const hipError_t e = launch_bgzf_archive(src, len, (uint32_t)bs, dynamic != 0, dst, dst_cap, total, sizes, ws, eof, stream);
+    if (e == hipErrorInvalidValue) return SWC_E_INVALID_ARGUMENT;
+    if (e != hipSuccess) return SWC_E_DEVICE;
+    bgzf::Result res;
+    if (hipMemcpyAsync(&res, ws + p.res, sizeof res, hipMemcpyDeviceToHost, stream) != hipSuccess) return SWC_E_DEVICE;
+    if (hipStreamSynchronize(stream) != hipSuccess) return SWC_E_DEVICE;
+    if (total_host) *total_host = res.total;
+    return res.status;
+}
+}  // namespace swc
+extern "C" {
+
+size_t swc_bgzf_bound(size_t len, size_t block_size) {
+    uint64_t bs = block_size;
+    if (!bgzf_block_size(bs)) return 0;
+    return len + 31 * (size_t)((len + bs - 1) / bs) + 28;
+}
+size_t swc_bgzf_workspace_bytes(size_t len, size_t block_size) {
+    uint64_t bs = block_size;
+    if (!bgzf_block_size(bs)) return 0;
+    return (size_t)bgzf::plan(len, bs).bytes + 16;   // (+ 16: the areas are cut from the first 16-byte boundary of the workspace)
+}
+
+int swc_batch_bgzf_archive(const uint8_t* src, uint64_t len, uint64_t block_size, int dynamic, uint8_t* dst, uint64_t dst_cap,
+                           uint64_t* total, uint64_t* member_sizes, void* workspace, size_t workspace_bytes, const swc_batch_opts* opts) try {
+    if (!bgzf_block_size(block_size) || (len && !src) || !dst || !total) return SWC_E_INVALID_ARGUMENT;
+    if (!device_ready()) return SWC_E_DEVICE;
+    if (opts && opts->device >= 0 && hipSetDevice(opts->device) != hipSuccess) return SWC_E_DEVICE;
+    hipStream_t stream = opts ? static_cast<hipStream_t>(opts->stream) : nullptr;
+    return bgzf_run(src, len, block_size, dynamic, dst, dst_cap, total, member_sizes, workspace, workspace_bytes, true, stream, nullptr);
+} catch (...) {
+    return SWC_E_DEVICE;
+}
+
+int swc_bgzf_archive(const uint8_t* data, size_t len, size_t block_size, int dynamic, uint8_t** out, size_t* out_len, size_t** sizes,
+                     size_t* n_members) try {
+    if (sizes) *sizes = nullptr;
+    if (n_members) *n_members = 0;
+    uint64_t bs = block_size;
+    if (!out || !out_len) return SWC_E_INVALID_ARGUMENT;
+    if ((len && !data) || !bgzf_block_size(bs)) { give_empty(out, out_len); return SWC_E_INVALID_ARGUMENT; }
+    if (!device_ready()) { give_empty(out, out_len); return SWC_E_DEVICE; }
+    hipStream_t stream = hipStreamPerThread;
+    const size_t n = (size_t)((len + bs - 1) / bs), per = std::max<size_t>(1, g_bgzf_round.load());
+    // the input once; per round: the packed bytes of up to `per` members, their sizes, the workspace
+    const size_t round_len = (size_t)std::min<uint64_t>(len, (uint64_t)per * bs), round_n = std::min(n, per);
+    const size_t dst_cap = swc_bgzf_bound(round_len, bs), ws_bytes = swc_bgzf_workspace_bytes(round_len, bs);
+    DevBuf d_src(len + 16), d_dst(dst_cap + 16), d_meta((round_n + 2) * sizeof(uint64_t)), d_ws(ws_bytes);
+    if (!d_src.ok() || !d_dst.ok() || !d_meta.ok() || !d_ws.ok()) { give_empty(out, out_len); return SWC_E_DEVICE; }
+    if (len && hipMemcpyAsync(d_src.ptr(), data, len, hipMemcpyHostToDevice, stream) != hipSuccess) { give_empty(out, out_len); return SWC_E_DEVICE; }
+    std::vector<size_t> msz;
+    std::vector<uint64_t> round_sizes(round_n + 1);
+    msz.reserve(n + 1);
+    uint8_t* res = host_result(swc_bgzf_bound(len, bs));   // (nothing below throws: the vectors have their room)
+    if (!res) throw std::bad_alloc();
+    uint64_t* d_total = reinterpret_cast<uint64_t*>(d_meta.ptr());
+    size_t pos = 0, done = 0;
+    int st = SWC_OK;
+    do {
+        const size_t m = std::min(per, n - done), lo = done * (size_t)bs, rl = std::min(len - lo, m * (size_t)bs);
+        const bool last = done + m == n;
+        uint64_t total = 0;
+        st = bgzf_run(d_src.u8() + lo, rl, bs, dynamic, d_dst.u8(), dst_cap, d_total, d_total + 1, d_ws.ptr(), ws_bytes, last, stream, &total);
+        if (st != SWC_OK) break;
+        // the round's bytes straight to their place in the result, its sizes behind the others'
+        const size_t cnt = m + (last ? 1 : 0);
+        if (hipMemcpyAsync(res + pos, d_dst.ptr(), total, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipMemcpyAsync(round_sizes.data(), d_total + 1, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipStreamSynchronize(stream) != hipSuccess) { st = SWC_E_DEVICE; break; }
+        for (size_t k = 0; k < cnt; k++) msz.push_back((size_t)round_sizes[k]);
+        pos += (size_t)total;
+        done += m;
+        stat_add(0, 1);
+        stat_add(1, (long long)m);
+    } while (done < n);
+    if (st != SWC_OK) { host_result_free(res); give_empty(out, out_len); return st; }
+    *out = res;
+    *out_len = pos;
+    if (sizes) *sizes = give_sizes(msz);
+    if (n_members) *n_members = msz.size();
+    return SWC_OK;
+} catch (...) {
+    if (out && out_len) give_empty(out, out_len);
+    return SWC_E_DEVICE;
 }
 
 int swc_zlib_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, size_t* out_len) try {

@@ -32,6 +32,7 @@
 #include "crc32_wave.h"
 #include "checksum_group.h"
 #include "delta_group.h"
+#include "bgzf_pack.h"
 #include "launch.h"
 
 namespace swc {
@@ -649,6 +650,40 @@ hipError_t launch_crc32(const Job* jobs, size_t n, uint32_t* crcs, hipStream_t s
     }
     hipLaunchKernelGGL(swc_crc32_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, jobs, (uint32_t)n, crcs);
     hipLaunchKernelGGL(swc_crc32_group_kernel, dim3((unsigned)(n < (size_t)kCrcGroupGrid ? n : (size_t)kCrcGroupGrid)), dim3(256), 0, stream, jobs, (uint32_t)n, crcs);
+    return hipGetLastError();
+}
+
+// ---- BGZF writer (bgzf_pack.h): job set-up | ONE compress launch over all members | CRC-32 of the chunks | offsets | pack -------
+__global__ __launch_bounds__(64) void swc_bgzf_setup_kernel(const uint8_t* src, uint64_t len, uint32_t bs, uint64_t n, Job* cj, Job* kj, uint8_t* slots, uint64_t stride) {
+    bgzf::setup_jobs<kWave>(blockIdx.x, src, len, bs, n, cj, kj, slots, stride);
+}
+__global__ __launch_bounds__(64) void swc_bgzf_scan_kernel(const Job* __restrict__ cj, uint64_t n, uint64_t* offs, uint64_t* sizes, uint64_t* total, bgzf::Result* res, uint64_t dst_cap, int eof) {
+    bgzf::scan_members<kWave>(cj, n, offs, sizes, total, res, dst_cap, eof != 0);
+}
+__global__ __launch_bounds__(64) void swc_bgzf_pack_kernel(uint64_t n, const Job* __restrict__ cj, const Job* __restrict__ kj, const uint32_t* __restrict__ crcs,
+                                                           const uint64_t* __restrict__ offs, const bgzf::Result* __restrict__ res, uint8_t* dst, int eof) {
+    bgzf::pack_wave<kWave>(blockIdx.x, n, cj, kj, crcs, offs, res, dst, eof != 0);
+}
+// `ws`: 16-byte aligned, bgzf::plan(len, bs).bytes of it.  Phase timing: compress (with the ordering pass) | CRC-32 | scan + pack.
+hipError_t launch_bgzf_archive(const uint8_t* src, uint64_t len, uint32_t bs, bool dynamic, uint8_t* dst, uint64_t dst_cap, uint64_t* total,
+                               uint64_t* sizes, uint8_t* ws, bool eof, hipStream_t stream) {
+    const bgzf::Plan p = bgzf::plan(len, bs);
+    if (p.n >= 0x7FFFFFFFull) return hipErrorInvalidValue;
+    Job* cj = reinterpret_cast<Job*>(ws + p.cjobs);
+    Job* kj = reinterpret_cast<Job*>(ws + p.kjobs);
+    uint32_t* crcs = reinterpret_cast<uint32_t*>(ws + p.crcs);
+    uint64_t* offs = reinterpret_cast<uint64_t*>(ws + p.offs);
+    bgzf::Result* res = reinterpret_cast<bgzf::Result*>(ws + p.res);
+    const size_t n = (size_t)p.n;
+    if (n) hipLaunchKernelGGL(swc_bgzf_setup_kernel, dim3((unsigned)((n + kWave - 1) / kWave)), dim3(kWave), 0, stream, src, len, bs, p.n, cj, kj, ws + p.slots, p.stride);
+    hipError_t e = dynamic ? launch_deflate_compress_dynamic(cj, n, stream) : launch_deflate_compress(cj, n, stream);
+    if (e != hipSuccess) return e;
+    e = launch_crc32(kj, n, crcs, stream);
+    if (e != hipSuccess) return e;
+    if (n) g_pt.mark(stream);
+    hipLaunchKernelGGL(swc_bgzf_scan_kernel, dim3(1), dim3(kWave), 0, stream, cj, p.n, offs, sizes, total, res, dst_cap, eof ? 1 : 0);
+    if (n + (eof ? 1 : 0)) hipLaunchKernelGGL(swc_bgzf_pack_kernel, dim3((unsigned)(n + (eof ? 1 : 0))), dim3(kWave), 0, stream, p.n, cj, kj, crcs, offs, res, dst, eof ? 1 : 0);
+    if (n) g_pt.mark(stream);
     return hipGetLastError();
 }
 

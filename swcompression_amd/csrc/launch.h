@@ -26,6 +26,10 @@ size_t lz4_ws_bytes_per_job(uint64_t cap);
 hipError_t launch_lz4_compress(Job* jobs, size_t n, hipStream_t stream);
 hipError_t launch_deflate_compress(Job* jobs, size_t n, hipStream_t stream);
 hipError_t launch_deflate_compress_dynamic(Job* jobs, size_t n, hipStream_t stream);
+// bgzf_pack.h: the whole BGZF writer on `stream` (set-up, one compress launch, CRC-32, offsets, pack); `ws`: 16-byte aligned device
+// memory of bgzf::plan(len, bs).bytes, the Result at its plan().res; eof: the end-of-file member behind the last one
+hipError_t launch_bgzf_archive(const uint8_t* src, uint64_t len, uint32_t bs, bool dynamic, uint8_t* dst, uint64_t dst_cap, uint64_t* total,
+                               uint64_t* sizes, uint8_t* ws, bool eof, hipStream_t stream);
 hipError_t launch_lzma(bool lzma2, Job* jobs, size_t n, void* spill, hipStream_t stream);
 size_t lzma_spill_bytes_per_job();
 hipError_t launch_bzip2(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStream_t stream);
