@@ -96,6 +96,14 @@ int swc_batch_decompress_ws(int codec, swc_job* jobs, size_t n, void* workspace,
  * out[0 .. min(out_len, out_cap)).  `jobs` and `crcs` are device pointers. */
 int swc_batch_crc32(const swc_job* jobs, size_t n, uint32_t* crcs, const swc_batch_opts* opts);
 
+/* swc_batch_decompress_ws and swc_batch_crc32 in one call: decodes the n jobs and leaves in crcs[i] (a device pointer to n
+ * words) what swc_batch_crc32 would compute afterwards, for every job whatever its status.  Deflate batches that take the
+ * wave copy kernel get the CRC-32 from that kernel: a wave that has written the last byte of its stream folds the stream
+ * it has just written, and no separate pass over the outputs runs.  Every other codec (and the small Deflate launches that take
+ * the workgroup kernel) decodes and then runs the CRC kernels. */
+int swc_batch_decompress_crc32_ws(int codec, swc_job* jobs, size_t n, void* workspace, size_t workspace_bytes, uint32_t* crcs,
+                                  const swc_batch_opts* opts);
+
 /* The other checksums of the archive layer over every job's output (same coverage rule), zero-extended to 64 bits:
  *   SWC_SUM_CRC32        CheckSums.crc32       CheckSums.swift:12-28  (GzipArchive.swift:99, XZArchive.swift:109-120)
  *   SWC_SUM_ADLER32      CheckSums.adler32     CheckSums.swift:48-57  (ZlibArchive.swift:38)

@@ -65,6 +65,7 @@ def load():
     sig("swc_batch_checksum", I, I, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(SwcBatchOpts))
     sig("swc_batch_workspace_bytes", C.c_size_t, I, C.c_size_t, C.c_uint64)
     sig("swc_batch_decompress_ws", I, I, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(SwcBatchOpts))
+    sig("swc_batch_decompress_crc32_ws", I, I, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(SwcBatchOpts))
     for n in ("swc_deflate_decompress", "swc_bzip2_decompress"):
         sig(n, I, C.c_char_p, C.c_size_t, u8pp, szp, szp)
     for n in ("swc_gzip_unarchive", "swc_zlib_unarchive", "swc_xz_unarchive", "swc_lzma_alone_decompress", "swc_lzma2_decompress_data"):

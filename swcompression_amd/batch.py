@@ -88,6 +88,7 @@ class DeviceBatch:
         self.d_ws = torch.empty(max(ws, 16), dtype=torch.uint8, device=self.device)
         self.ws_bytes = ws
         self._crc_buf = None
+        self._crc_current = False   # _crc_buf holds the CRC-32 of what the latest launch wrote
         torch.cuda.synchronize(self.device)
 
     @property
@@ -95,16 +96,27 @@ class DeviceBatch:
         return int(self.in_lens.sum())
 
     def launch(self, sync=False):
+        """One launch over all jobs.  A Deflate batch whose CRCs have been asked for once (crc32_async() has allocated the
+        buffer) keeps them current from then on: the launch goes through swc_batch_decompress_crc32_ws, whose copy kernel
+        leaves the CRC-32 of every output in the buffer."""
         torch = self.torch
         opts = _lib.SwcBatchOpts(self.device.index if self.device.index is not None else -1,
                                  torch.cuda.current_stream(self.device).cuda_stream, 1 if sync else 0, 0)
-        st = self.lib.swc_batch_decompress_ws(self.codec, self.d_jobs.data_ptr(), self.n, self.d_ws.data_ptr(),
-                                              self.ws_bytes, C.byref(opts))
+        self._crc_current = False
+        if self.codec == CODECS["deflate"] and self._crc_buf is not None:
+            st = self.lib.swc_batch_decompress_crc32_ws(self.codec, self.d_jobs.data_ptr(), self.n, self.d_ws.data_ptr(),
+                                                        self.ws_bytes, self._crc_buf.data_ptr(), C.byref(opts))
+            self._crc_current = st == 0
+        else:
+            st = self.lib.swc_batch_decompress_ws(self.codec, self.d_jobs.data_ptr(), self.n, self.d_ws.data_ptr(),
+                                                  self.ws_bytes, C.byref(opts))
         if st:
             raise RuntimeError("swc_batch_decompress failed with status %d" % st)
 
     def crc32(self):
-        """CRC-32 of every job's output, computed on the device (swc_batch_crc32).  Returns a numpy uint32 array."""
+        """CRC-32 of every job's output, computed on the device (swc_batch_crc32).  Returns a numpy uint32 array.  Always the
+        standalone kernels over the bytes that lie in memory: an independent check of what a fused launch left in the buffer
+        of crc32_async()."""
         torch = self.torch
         d = torch.empty(self.n, dtype=torch.int32, device=self.device)
         opts = _lib.SwcBatchOpts(self.device.index if self.device.index is not None else -1,
@@ -116,8 +128,11 @@ class DeviceBatch:
 
     def crc32_async(self):
         """swc_batch_crc32 on the current stream, no synchronisation, result left on the device (bench.py: the CRC-32 of
-        every gzip member is part of the timed step)."""
+        every gzip member is part of the timed step).  Returns at once when the buffer already belongs to the latest launch
+        (launch() of a Deflate batch keeps it current once this method has allocated it); wipe_results() ends that."""
         torch = self.torch
+        if self._crc_current:
+            return
         if self._crc_buf is None:
             self._crc_buf = torch.empty(self.n, dtype=torch.int32, device=self.device)
         opts = _lib.SwcBatchOpts(self.device.index if self.device.index is not None else -1,
@@ -142,7 +157,9 @@ class DeviceBatch:
 
     def wipe_results(self):
         """Zeroes every job's output range, the result fields of the job records and the CRC buffer (bench.py: what is
-        verified after the timed region must come from the last timed step, not from the warm-up)."""
+        verified after the timed region must come from the last timed step, not from the warm-up).  The CRC buffer no longer
+        belongs to a launch afterwards: the next crc32_async() without a launch computes it from what lies in memory."""
+        self._crc_current = False
         self.d_out.zero_()
         jobs = self._jobs_host.copy()
         jobs["status"] = 902

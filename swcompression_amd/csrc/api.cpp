@@ -358,8 +358,15 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
         tr.mark("stage inputs (pinned)", up_bytes);
         if (hipMemcpyAsync(d_in, up, up_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return SWC_E_DEVICE;
         const uint64_t* d_off = !ws_off.empty() ? reinterpret_cast<const uint64_t*>(d_jobs + jobs_bytes) : nullptr;
-        if (launch_codec(codec, reinterpret_cast<Job*>(d_jobs), m, d_ws.ptr(), ws_bytes, stream, d_off) != hipSuccess) return SWC_E_DEVICE;
-        if (sum_kind && launch_checksum(sum_kind, reinterpret_cast<const Job*>(d_jobs), m, reinterpret_cast<uint64_t*>(d_sums), stream) != hipSuccess) return SWC_E_DEVICE;
+        // Deflate units that want their CRC-32 (gzip members, ZIP entries): the copy kernel leaves it, as 32-bit words in the
+        // first half of the checksum area (widened on the way down)
+        const bool fused_crc = codec == SWC_CODEC_DEFLATE && sum_kind == SWC_SUM_CRC32;
+        if (fused_crc) {
+            if (launch_inflate(reinterpret_cast<Job*>(d_jobs), m, d_ws.ptr(), ws_bytes, stream, d_off, reinterpret_cast<uint32_t*>(d_sums)) != hipSuccess) return SWC_E_DEVICE;
+        } else {
+            if (launch_codec(codec, reinterpret_cast<Job*>(d_jobs), m, d_ws.ptr(), ws_bytes, stream, d_off) != hipSuccess) return SWC_E_DEVICE;
+            if (sum_kind && launch_checksum(sum_kind, reinterpret_cast<const Job*>(d_jobs), m, reinterpret_cast<uint64_t*>(d_sums), stream) != hipSuccess) return SWC_E_DEVICE;
+        }
         stat_add(0, 1);
         stat_add(1, (long long)m);
         // device -> host: the job records (they say how much of every output exists), the checksums, the outputs
@@ -414,7 +421,7 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
             const size_t produced = (size_t)std::min<uint64_t>(j.out_len, j.out_cap);
             u.out_size = produced;
             u.in_dst = u.dst != nullptr && produced <= u.dst_cap;
-            if (sum_kind && u.sum_kind == sum_kind) { u.sum = sums[k]; u.sum_valid = true; }
+            if (sum_kind && u.sum_kind == sum_kind) { u.sum = fused_crc ? reinterpret_cast<const uint32_t*>(sums)[k] : sums[k]; u.sum_valid = true; }
             done.push_back(CopyOut{&u, outs + out_off[k], produced});
         }
         copy_out(done);
@@ -520,6 +527,24 @@ int swc_batch_decompress_ws(int codec, swc_job* jobs, size_t n, void* workspace,
     hipError_t e = launch_codec(codec, reinterpret_cast<Job*>(jobs), n, workspace, workspace_bytes, stream);
     if (e == hipErrorInvalidValue) return SWC_E_INVALID_ARGUMENT;
     if (e != hipSuccess) return SWC_E_DEVICE;
+    if (opts && opts->synchronize && hipStreamSynchronize(stream) != hipSuccess) return SWC_E_DEVICE;
+    return SWC_OK;
+} catch (...) {   // std::bad_alloc / length_error from a size taken from the input: never through the C boundary
+    return SWC_E_DEVICE;
+}
+
+int swc_batch_decompress_crc32_ws(int codec, swc_job* jobs, size_t n, void* workspace, size_t workspace_bytes, uint32_t* crcs,
+                                  const swc_batch_opts* opts) try {
+    if (!device_ready()) return SWC_E_DEVICE;
+    if (n && (!jobs || !crcs)) return SWC_E_INVALID_ARGUMENT;
+    if (opts && opts->device >= 0 && hipSetDevice(opts->device) != hipSuccess) return SWC_E_DEVICE;
+    hipStream_t stream = opts ? static_cast<hipStream_t>(opts->stream) : nullptr;
+    // Deflate: the copy kernel ends with the CRC of the stream it has written (launch_inflate); any other codec: decode, then the CRC kernels
+    hipError_t e = codec == SWC_CODEC_DEFLATE ? launch_inflate(reinterpret_cast<Job*>(jobs), n, workspace, workspace_bytes, stream, nullptr, crcs)
+                                              : launch_codec(codec, reinterpret_cast<Job*>(jobs), n, workspace, workspace_bytes, stream);
+    if (e == hipErrorInvalidValue) return SWC_E_INVALID_ARGUMENT;
+    if (e != hipSuccess) return SWC_E_DEVICE;
+    if (codec != SWC_CODEC_DEFLATE && launch_crc32(reinterpret_cast<const Job*>(jobs), n, crcs, stream) != hipSuccess) return SWC_E_DEVICE;
     if (opts && opts->synchronize && hipStreamSynchronize(stream) != hipSuccess) return SWC_E_DEVICE;
     return SWC_OK;
 } catch (...) {   // std::bad_alloc / length_error from a size taken from the input: never through the C boundary

@@ -30,6 +30,7 @@
 #include "bzip2_team.h"
 #include "crc32_group.h"
 #include "crc32_wave.h"
+#include "crc32_tail.h"
 #include "checksum_group.h"
 #include "delta_group.h"
 #include "bgzf_pack.h"
@@ -172,14 +173,30 @@ __global__ __launch_bounds__(kInflateResolveThreads) void swc_lz_resolve_kernel(
 //            flush moved to the top of the iteration, which needs 3,328);
 //   LZ4      7 KiB window, 3.25 KiB kept, groups of up to 1 KiB, runs of up to 32 literal bytes per lane, 81 VGPRs -> 20 waves per CU
 //            (9 KiB / 2 KiB groups / 16 waves: 57.9 against 56.6 ms).
-template <typename CFG, int RM = 0>
-__device__ __forceinline__ void lz_copy_body(const Job* __restrict__ jobs, uint32_t n, const WsMap& wm, const uint32_t* __restrict__ order) {
+// CRC (Deflate, swc_lz_copy_crc32_kernel further down): when copy_job has returned -- on whichever path: no literal stream, no
+// records, a failed stream -- the window is dead, and the wave ends with the CRC-32 of its own output in crcs[g] (crc32_tail.h).
+constexpr uint64_t kCrcGroupLen = 1u << 20;   // CRC-32 of a stream: by one wave below, by a 256-thread group from here on
+extern __device__ crcw::WaveConsts g_crc_consts;
+template <typename CFG, int RM = 0, bool CRC = false>
+__device__ __forceinline__ void lz_copy_body(const Job* __restrict__ jobs, uint32_t n, const WsMap& wm, const uint32_t* __restrict__ order, uint32_t* __restrict__ crcs = nullptr) {
     __shared__ __attribute__((aligned(16))) lzc::Lds<CFG::kWin> lds;
     uint32_t g = job_of(order, blockIdx.x, n);
     if (g >= n) return;
     Job job = jobs[g];
-    if (job.dict != nullptr) return;   // (LZ4 blocks with a dictionary prefix were decoded by the lane kernel)
-    lzc::copy_job<CFG, RM>(job, wm.area(g), wm.bytes(g), &lds);
+    if constexpr (!CRC) {
+        if (job.dict != nullptr) return;   // (LZ4 blocks with a dictionary prefix were decoded by the lane kernel)
+        lzc::copy_job<CFG, RM>(job, wm.area(g), wm.bytes(g), &lds);
+    } else {
+        static_assert(sizeof(crct::TailConsts) <= CFG::kWin, "the constants of the tail go where the window was");
+        if (job.dict == nullptr) lzc::copy_job<CFG, RM>(job, wm.area(g), wm.bytes(g), &lds);
+        // what swc_batch_crc32 covers; streams of a megabyte and more (the 64-bit positions among them) are left to
+        // swc_crc32_group_kernel, which the launch puts behind this kernel
+        const uint64_t len = job.out_len < job.out_cap ? job.out_len : job.out_cap;
+        if (len >= kCrcGroupLen) return;
+        simt::vmem_fence();   // every store of this wave has arrived (what drain() waits for)
+        const uint32_t c = crct::crc32_tail((gcptr)job.out, simt::uniform((uint32_t)len), (crct::TailConsts*)lds.win, &g_crc_consts);
+        if (threadIdx.x == 0) crcs[g] = c;
+    }
 }
 #ifndef SWC_LZC_WAVES
 #define SWC_LZC_WAVES 6
@@ -197,6 +214,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZC_WAVE
 }
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZC4_WAVES, SWC_LZC4_WAVES))) void swc_lz4_copy_kernel(const Job* __restrict__ jobs, uint32_t n, WsMap wm, const uint32_t* __restrict__ order) {
     lz_copy_body<lzc::CfgLz4, SWC_LZ4_RECORD_MODE>(jobs, n, wm, order);   // (the literals come from the block itself)
+}
+// The Deflate copy kernel that ends with the stream's CRC-32: the same body, the same window, the same 24 waves per CU.  A kernel
+// of its own, so that swc_lz_copy_kernel keeps its instructions and its 40 VGPRs (the tail holds four rows of the stream in flight).
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZC_WAVES, SWC_LZC_WAVES))) void swc_lz_copy_crc32_kernel(const Job* __restrict__ jobs, uint32_t n, WsMap wm, const uint32_t* __restrict__ order, uint32_t* __restrict__ crcs) {
+    lz_copy_body<lzc::CfgDeflate, 0, true>(jobs, n, wm, order, crcs);
 }
 // "lz_copier" (swc_set_tuning): 1 = lz_copy.h with the windows above (default), 0 = the byte-cell resolver of lz_resolve.h
 // (rounds 2-4) -- both produce the same bytes.
@@ -250,8 +272,35 @@ static std::atomic<int> g_deflate_team{1};
 void set_deflate_team(int v) { g_deflate_team = v; }
 constexpr size_t kTeamMaxStreams = 256, kTeamForceStreams = 4096;
 
-hipError_t launch_inflate(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStream_t stream, const uint64_t* ws_off) {
+// Phase 2 of a Deflate launch and, with `crcs`, the CRC-32 of every output behind it -- what launch_crc32 would leave there.  The
+// wave kernel folds the CRC of the streams below kCrcGroupLen into its tail and the group kernel takes the rest (none in a batch
+// of small members: it ends after one read of the lengths); behind the workgroup kernel the two CRC kernels run as they always
+// did.  ONE phase mark, behind the kernel that copies: a Deflate launch has two phases with or without the CRCs.
+static hipError_t crc32_consts_ready(hipStream_t stream);
+static void launch_crc32_group(const Job* jobs, size_t n, uint32_t* crcs, hipStream_t stream);
+static void launch_inflate_phase2(Job* jobs, size_t n, const WsMap& wm, const uint32_t* order, uint32_t* crcs, hipStream_t stream) {
+    if (wave_copier(n)) {
+        if (crcs) {
+            hipLaunchKernelGGL(swc_lz_copy_crc32_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, jobs, (uint32_t)n, wm, order, crcs);
+            g_pt.mark(stream);
+            launch_crc32_group(jobs, n, crcs, stream);
+            return;
+        }
+        launch_lz_copy(false, jobs, n, wm, order, stream);
+        g_pt.mark(stream);
+        return;
+    }
+    hipLaunchKernelGGL(swc_lz_resolve_kernel, dim3((unsigned)n), dim3(kInflateResolveThreads), 0, stream, jobs, (uint32_t)n, wm, g_prof, order);
+    g_pt.mark(stream);
+    if (crcs) (void)launch_crc32(jobs, n, crcs, stream);   // (hipGetLastError in the caller)
+}
+
+hipError_t launch_inflate(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStream_t stream, const uint64_t* ws_off, uint32_t* crcs) {
     if (n == 0) return hipSuccess;
+    if (crcs) {   // (the first call on a device builds the constants and waits for them: in front of the phase timer)
+        const hipError_t e = crc32_consts_ready(stream);
+        if (e != hipSuccess) return e;
+    }
     size_t stride = ws ? (ws_bytes / n) & ~(size_t)15 : 0;
     if (!ws_off && stride < sizeof(lzr::StreamHeader)) return hipErrorInvalidValue;
     const WsMap wm{(uint8_t*)ws, stride, ws_off};
@@ -266,10 +315,7 @@ hipError_t launch_inflate(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStr
             (void)launch_inflate_team(jobs, n, (uint8_t*)ws, stride, ws_off, (uint8_t*)scratch, stream);   // (hipGetLastError below)
             g_pt.mark(stream);
             (void)hipFreeAsync(scratch, stream);
-            const bool copier = wave_copier(n);
-            if (copier) launch_lz_copy(false, jobs, n, wm, nullptr, stream);
-            else hipLaunchKernelGGL(swc_lz_resolve_kernel, dim3((unsigned)n), dim3(kInflateResolveThreads), 0, stream, jobs, (uint32_t)n, wm, g_prof, (const uint32_t*)nullptr);
-            g_pt.mark(stream);
+            launch_inflate_phase2(jobs, n, wm, nullptr, crcs, stream);
             return hipGetLastError();
         }
         (void)hipGetLastError();   // no room for the rows: one wavefront per stream
@@ -279,10 +325,7 @@ hipError_t launch_inflate(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStr
     const uint32_t* order = job_order(jobs, n, stream);
     hipLaunchKernelGGL(swc_inflate_sync_kernel, dim3((unsigned)n), block, 0, stream, jobs, (uint32_t)n, wm, g_prof, order);
     g_pt.mark(stream);
-    const bool copier = wave_copier(n);
-    if (copier) launch_lz_copy(false, jobs, n, wm, order, stream);
-    else hipLaunchKernelGGL(swc_lz_resolve_kernel, dim3((unsigned)n), dim3(kInflateResolveThreads), 0, stream, jobs, (uint32_t)n, wm, g_prof, order);
-    g_pt.mark(stream);
+    launch_inflate_phase2(jobs, n, wm, order, crcs, stream);
     return hipGetLastError();
 }
 
@@ -583,8 +626,7 @@ hipError_t launch_bzip2(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStrea
 // Two kernels, both launched over all n jobs, each taking the jobs of its size class (the sizes are on the device; a wave or
 // group whose job belongs to the other kernel ends at once): one stream per WAVE below 1 MB (crc32_wave.h: no per-stream
 // set-up, no barrier after the constants are in LDS), one stream per 256-thread group above (crc32_group.h).
-constexpr uint64_t kCrcGroupLen = 1u << 20;
-__device__ crcw::WaveConsts g_crc_consts;
+__device__ crcw::WaveConsts g_crc_consts;   // (kCrcGroupLen: above lz_copy_body, whose tail takes the streams below it)
 __global__ __launch_bounds__(256) void swc_crc32_consts_kernel() { crcw::build_consts<256>(&g_crc_consts, (int)threadIdx.x); }
 
 __global__ __launch_bounds__(256) void swc_crc32_kernel(const Job* __restrict__ jobs, uint32_t n, uint32_t* __restrict__ crcs) {
@@ -633,23 +675,30 @@ __global__ __launch_bounds__(256) void swc_crc32_group_kernel(const Job* __restr
     }
 }
 
+// the constants, once per device (the first call on a device builds them on the caller's stream; later launches on any
+// stream of the device come after it in host time and, through the wait below, in device time)
+static hipError_t crc32_consts_ready(hipStream_t stream) {
+    static std::mutex mu;
+    static bool built[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+    std::lock_guard<std::mutex> lk(mu);
+    if (!built[dev]) {
+        hipLaunchKernelGGL(swc_crc32_consts_kernel, dim3(1), dim3(256), 0, stream);
+        if (hipStreamSynchronize(stream) != hipSuccess) return hipErrorUnknown;
+        built[dev] = true;
+    }
+    return hipSuccess;
+}
+static void launch_crc32_group(const Job* jobs, size_t n, uint32_t* crcs, hipStream_t stream) {
+    hipLaunchKernelGGL(swc_crc32_group_kernel, dim3((unsigned)(n < (size_t)kCrcGroupGrid ? n : (size_t)kCrcGroupGrid)), dim3(256), 0, stream, jobs, (uint32_t)n, crcs);
+}
 hipError_t launch_crc32(const Job* jobs, size_t n, uint32_t* crcs, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    {   // the constants, once per device (the first call on a device builds them on the caller's stream; later launches on any
-        // stream of the device come after it in host time and, through the wait below, in device time)
-        static std::mutex mu;
-        static bool built[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        std::lock_guard<std::mutex> lk(mu);
-        if (!built[dev]) {
-            hipLaunchKernelGGL(swc_crc32_consts_kernel, dim3(1), dim3(256), 0, stream);
-            if (hipStreamSynchronize(stream) != hipSuccess) return hipErrorUnknown;
-            built[dev] = true;
-        }
-    }
+    const hipError_t e = crc32_consts_ready(stream);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(swc_crc32_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, jobs, (uint32_t)n, crcs);
-    hipLaunchKernelGGL(swc_crc32_group_kernel, dim3((unsigned)(n < (size_t)kCrcGroupGrid ? n : (size_t)kCrcGroupGrid)), dim3(256), 0, stream, jobs, (uint32_t)n, crcs);
+    launch_crc32_group(jobs, n, crcs, stream);
     return hipGetLastError();
 }
 

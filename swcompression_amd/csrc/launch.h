@@ -5,7 +5,9 @@
 #include "swc_common.h"
 namespace swc {
 // ws_off != nullptr: device array of n + 1 prefix-summed per-job workspace offsets (then ws_bytes is ignored)
-hipError_t launch_inflate(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStream_t stream, const uint64_t* ws_off = nullptr);
+// crcs != nullptr: device array of n words that the launch leaves as launch_crc32 would (the wave copy kernel folds the CRC-32 of
+// a stream into its tail; behind the workgroup kernel the CRC kernels run)
+hipError_t launch_inflate(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStream_t stream, const uint64_t* ws_off = nullptr, uint32_t* crcs = nullptr);
 // inflate_team.hip: phase 1 with a team of wavefronts per stream (launches of few streams); `scratch`: inflate_team_scratch_bytes(n)
 size_t inflate_team_scratch_bytes(size_t n);
 hipError_t launch_inflate_team(Job* jobs, size_t n, uint8_t* ws, size_t stride, const uint64_t* ws_off, uint8_t* scratch, hipStream_t stream);
