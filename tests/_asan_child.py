@@ -110,6 +110,39 @@ for kind, size in (("text", 120000), ("bin", 90000), ("mix", 80000), ("rand", 20
             assert run_lzma2(z, p, mode, cap=len(p) // 2)[1] == 901
             n += 3
 
+# LZMA / LZMA2 streams built decision by decision (_lzma_build.py): lc + lp up to 12 fills the whole workspace, property changes re-map
+# the cached lines, matches reach back to the first byte of the output and end on its last; the error cases stop in mid-symbol
+import _lzma_build  # noqa: E402
+
+
+def run_built(c, mode, cap):
+    j = (Job * 1)()
+    ib = libc.malloc(max(len(c.stream), 1))
+    C.memmove(ib, c.stream, len(c.stream))
+    ob = libc.malloc(max(cap, 1))
+    j[0].in_, j[0].in_len, j[0].out, j[0].out_cap = ib, len(c.stream), ob, cap
+    if c.kind == "lzma2":
+        j[0].aux = c.dict_byte
+    else:
+        lc, lp, pb, ds, declared = c.props
+        j[0].aux, j[0].dict, j[0].dict_len = lc | lp << 8 | pb << 16, ds or None, declared & 0xFFFFFFFFFFFFFFFF
+    lib.emu_lzma_mode(j, 1, 1 if c.kind == "lzma2" else 0, mode)
+    got = (j[0].status, C.string_at(ob, min(j[0].out_len, cap)), j[0].in_consumed)
+    libc.free(ib)
+    libc.free(ob)
+    return got
+
+
+for c in _lzma_build.directed_cases():
+    for mode in (0, 1):
+        if c.status == 0:
+            assert run_built(c, mode, len(c.plain)) == (0, c.plain, c.consumed), ("built", c.name, mode)
+            assert run_built(c, mode, len(c.plain) - 1)[0] == (901 if len(c.plain) > 1 else 0), ("built, capacity - 1", c.name, mode)   # (one byte of output: the buffer cannot be smaller)
+            n += 2
+        else:
+            assert run_built(c, mode, 80000)[0] == c.status, ("built", c.name, mode)
+            n += 1
+
 # the wave-per-stream CRC-32: 16-byte loads at every alignment must stay inside an exact-size buffer
 import zlib
 lib.emu_crc32_wave.argtypes = [C.c_void_p, C.c_size_t]

@@ -7,6 +7,7 @@ import struct
 import numpy as np
 import pytest
 
+import _lzma_build as B
 import _oracle as O
 import _streams as S
 import swcompression_amd as swc
@@ -216,3 +217,84 @@ def test_literal_coder_cache_against_whole_model():
     for k in range(len(units)):
         assert outs[1][k] == want[k], ("cache", k)
         assert outs[0][k] == want[k], ("whole model", k)
+
+
+# ------------------------------------------------------------------------ streams built decision by decision (tests/_lzma_build.py)
+@pytest.fixture(scope="module")
+def built():
+    """The directed set and the oracle's word on it, computed once and never changed; each case held to the KIND of result it was
+    built for."""
+    cases = B.directed_cases()
+    exp = [O.lzma2(c.stream, c.dict_byte) if c.kind == "lzma2" else O.lzma_raw(c.stream, *c.props) for c in cases]
+    for c, e in zip(cases, exp):
+        assert e == (0, c.plain, c.consumed) if c.status == 0 else e[0] == c.status, c.name
+    return cases, exp
+
+
+def _built_batch(cases, exp, kind, tile, label):
+    """All cases of one kind in one launch, `tile` copies of each at addresses of their own; valid streams at EXACT capacity."""
+    idx = [i for i, c in enumerate(cases) if c.kind == kind]
+    caps = [max(len(exp[i][1]), 1) if exp[i][0] == 0 else len(exp[i][1]) + 300 for i in idx]
+    if kind == "lzma2":
+        b = DeviceBatch("lzma2", [cases[i].stream for i in idx], caps, aux=[cases[i].dict_byte for i in idx], tile=tile)
+    else:
+        p = [cases[i].props for i in idx]
+        b = DeviceBatch("lzma", [cases[i].stream for i in idx], caps, aux=[lc | lp << 8 | pb << 16 for lc, lp, pb, _, _ in p],
+                        extra=[q[4] & 0xFFFFFFFFFFFFFFFF for q in p], dict_values=[q[3] for q in p], tile=tile)
+    b.launch(sync=True)
+    r = b.results()
+    assert b.n == len(idx) * tile
+    for j in range(b.n):
+        c, e = cases[idx[j % len(idx)]], exp[idx[j % len(idx)]]
+        what = "%s, %s (copy %d)" % (label, c.name, j // len(idx))
+        assert int(r["status"][j]) == e[0], "status %d, oracle %d: %s" % (int(r["status"][j]), e[0], what)
+        if e[0] == 0:
+            assert int(r["out_len"][j]) == len(e[1]) and int(r["in_consumed"][j]) == e[2], what
+            assert b.output(j, len(e[1])) == e[1], "bytes differ: " + what
+    return len(idx)
+
+
+@pytest.mark.parametrize("coder_cache", [1, 0], ids=["coder-cache", "coders-in-lds"])
+@pytest.mark.parametrize("kind", ["lzma2", "lzma"])
+def test_built_streams_directed(built, kind, coder_cache):
+    """What liblzma never writes (tests/_lzma_build.py: directed_cases) on the device, where the copy of a match is spread over 64
+    lanes and the literal behind it takes its coder from the lane that wrote the last byte: every (distance, length) class of
+    copy_match(), property changes that re-map the cached lines, lc + lp up to 12 in the workspace, the spilled `high` trees of both
+    length coders, dictionary resets in mid-stream, 0x80 behind stored chunks.  Four copies of every case in one launch, so that
+    several waves of a SIMD work on different cases at once; both layouts of the model."""
+    from swcompression_amd import _lib
+    lib = _lib.load()
+    cases, exp = built
+    try:
+        assert lib.swc_set_tuning(b"lzma_coder_cache", coder_cache) == 0
+        assert _built_batch(cases, exp, kind, 4, "coder cache %d" % coder_cache) >= (150 if kind == "lzma2" else 20)
+    finally:
+        lib.swc_set_tuning(b"lzma_coder_cache", 1)
+
+
+def test_built_streams_single_shot(built):
+    """Built streams through the public calls: one stream per launch, and for lc + lp > 4 the run without a workspace that
+    reports SWC_E_NEED_WORKSPACE and is repeated with one."""
+    cases, exp = built
+    names = ["properties-3-to-12-to-3", "properties-4-to-0-to-4-with-dictionary-resets", "model-lc8-lp4-pb4-lzma2", "model-lc6-lp0-pb2-lzma2",
+             "0x80-behind-a-stored-chunk-that-reset-the-dictionary", "end-marker-at-exactly-unpack", "dictionary-reset-0xE0-mid-stream-64-times",
+             "copy-shapes-lc8-distances-36-to-4095-matches", "garbage-behind-the-terminator", "end-marker-before-unpack",
+             "state-11-pos-state-15-short-rep0-traps", "chunk-header-at-window-offset-207-cut-by-3",
+             "model-lc8-lp4-pb4-lzma", "model-lc5-lp0-pb2-lzma", "raw-lzma-dictionary-of-1-bytes-end-marker", "raw-lzma-dictionary-of-0-bytes-declared-size",
+             "raw-lzma-declared-size-then-end-marker", "raw-lzma-end-marker-with-code-not-zero", "raw-lzma-declared-size-reached-with-code-not-zero"]
+    by_name = {c.name: (c, e) for c, e in zip(cases, exp)}
+    for name in names:
+        c, e = by_name[name]
+        if c.kind == "lzma2":
+            call = lambda: swc.LZMA2.decompress_raw(c.stream, c.dict_byte)
+            want = (e[1], e[2])
+        else:
+            lc, lp, pb, ds, declared = c.props
+            call = lambda: swc.LZMA.decompress(c.stream, swc.LZMAProperties(lc, lp, pb, ds), None if declared < 0 else declared)
+            want = e[1]
+        if e[0] == 0:
+            assert call() == want, name
+        else:
+            with pytest.raises(swc.SWCError) as ei:
+                call()
+            assert ei.value.status == e[0], name

@@ -19,6 +19,7 @@ import random
 import pytest
 
 import _deflate_build as B
+import _lzma_build as LB
 import _oracle as O
 import _soak as K
 from swcompression_amd.batch import DeviceBatch
@@ -39,8 +40,8 @@ def _both_kernels(fn):
         lib.swc_set_tuning(b"lz_copier", 1)
 
 
-def _check(codec, streams, exp, caps, label, aux=None):
-    b = DeviceBatch(codec, streams, caps, aux=aux)
+def _check(codec, streams, exp, caps, label, aux=None, extra=None, dict_values=None):
+    b = DeviceBatch(codec, streams, caps, aux=aux, extra=extra, dict_values=dict_values)
     b.launch(sync=True)
     r = b.results()
     for i, e in enumerate(exp):
@@ -153,6 +154,34 @@ def test_lzma2_units_of_random_encoder_settings(seed):
             lib.swc_set_tuning(b"lzma_coder_cache", 1)
     finally:
         O.lib.refcpu_set_max_output(1 << 30)
+
+
+@pytest.mark.parametrize("seed", range(ROUNDS))
+def test_lzma_streams_built_decision_by_decision(seed):
+    """Streams no encoder writes (tests/_lzma_build.py: every chunk control in any order, property changes and dictionary resets in
+    mid-stream, lc + lp up to 12, matches across resets, end markers inside chunks, raw LZMA with dictionaries of a few bytes); half
+    of them restricted to what liblzma decodes.  100 per seed, LZMA2 and raw LZMA each in one launch, both layouts of the model."""
+    from swcompression_amd import _lib
+    lib = _lib.load()
+    rnd = random.Random(0x12A4B50AC + seed)
+    cases = [LB.random_stream(rnd, rnd.choice([1, 9, 300, 4000, 20000]), i % 2 == 0) for i in range(100)]
+    exp = [O.lzma2(c.stream, c.dict_byte) if c.kind == "lzma2" else O.lzma_raw(c.stream, *c.props) for c in cases]
+    for i, (c, e) in enumerate(zip(cases, exp)):
+        assert e == (0, c.plain, c.consumed), "the builder and the oracle disagree on a stream it built (seed %d, stream %d)" % (seed, i)
+    l2 = [i for i, c in enumerate(cases) if c.kind == "lzma2"]
+    l1 = [i for i, c in enumerate(cases) if c.kind == "lzma"]
+    assert l1 and l2
+    caps = [max(len(c.plain), 1) for c in cases]      # exact capacity
+    try:
+        for mode in (1, 0):
+            assert lib.swc_set_tuning(b"lzma_coder_cache", mode) == 0
+            label = "seed %d, coder cache %d" % (seed, mode)
+            _check("lzma2", [cases[i].stream for i in l2], [exp[i] for i in l2], [caps[i] for i in l2], label + ", LZMA2", aux=[cases[i].dict_byte for i in l2])
+            p = [cases[i].props for i in l1]
+            _check("lzma", [cases[i].stream for i in l1], [exp[i] for i in l1], [caps[i] for i in l1], label + ", raw LZMA",
+                   aux=[lc | lp << 8 | pb << 16 for lc, lp, pb, _, _ in p], extra=[q[4] & 0xFFFFFFFFFFFFFFFF for q in p], dict_values=[q[3] for q in p])
+    finally:
+        lib.swc_set_tuning(b"lzma_coder_cache", 1)
 
 
 @pytest.mark.parametrize("seed", range(ROUNDS))

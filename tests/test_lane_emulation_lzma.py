@@ -1,11 +1,13 @@
 """CPU tier: the LZMA / LZMA2 wave decoder (swcompression_amd/csrc/lzma_wave.h) built for the host as a
 single logical lane vs the oracle (reference Sources/LZMA/*.swift, Sources/LZMA2/*.swift)."""
+import functools
 import lzma as _pylzma
 
 import numpy as np
 import pytest
 
 import _emu as E
+import _lzma_build as B
 import _oracle as O
 import _streams as S
 
@@ -134,3 +136,67 @@ def test_random_payload_mixtures_every_model_shape():
         assert r[0] == e[0], p       # (pb = 4: a valid stream can reach the index the reference traps on)
         if e[0] == 0:
             assert r[:3] == (0, x, len(z)) and e[1] == x, p
+
+
+# ------------------------------------------------------------------------ streams built decision by decision (tests/_lzma_build.py)
+@functools.lru_cache(maxsize=None)
+def _directed_expectations():
+    """The oracle on the directed set of _lzma_build.py, computed once; each case held to the KIND of result it was built for (a
+    builder that drifted would otherwise turn the comparison into oracle == kernel on the wrong streams)."""
+    cases = B.directed_cases()
+    exp = [O.lzma2(c.stream, c.dict_byte) if c.kind == "lzma2" else O.lzma_raw(c.stream, *c.props) for c in cases]
+    for c, e in zip(cases, exp):
+        assert e == (0, c.plain, c.consumed) if c.status == 0 else e[0] == c.status, c.name
+    return cases, exp
+
+
+def _emulate(cases, caps):
+    """Built cases of both kinds through the emulated kernel, in the order given."""
+    res = [None] * len(cases)
+    i2 = [i for i, c in enumerate(cases) if c.kind == "lzma2"]
+    i1 = [i for i, c in enumerate(cases) if c.kind == "lzma"]
+    for i, r in zip(i2, E.lzma2([cases[i].stream for i in i2], [caps[i] for i in i2], [cases[i].dict_byte for i in i2])):
+        res[i] = r
+    for i, r in zip(i1, E.lzma([cases[i].stream for i in i1], [caps[i] for i in i1], [cases[i].props[:3] for i in i1],
+                               [cases[i].props[3] for i in i1], [cases[i].props[4] for i in i1])):
+        res[i] = r
+    return res
+
+
+def _check_built(cases, exp, res, label=""):
+    for c, e, r in zip(cases, exp, res):
+        assert r[0] == e[0], "%s%s: status %d, oracle %d" % (label, c.name, r[0], e[0])
+        if e[0] == 0:
+            assert r[3] == len(e[1]) and r[2] == e[2], "%s%s: %d bytes out, %d consumed; oracle %d, %d" % (label, c.name, r[3], r[2], len(e[1]), e[2])
+            assert r[1] == e[1], "%s%s: bytes differ" % (label, c.name)
+
+
+def test_built_streams_directed():
+    """What liblzma never writes (tests/_lzma_build.py: directed_cases): property changes and dictionary resets in mid-stream, 0x80
+    behind a stored chunk, lc + lp up to 12, every packet kind from every state, every length through both coders, every pos slot
+    up to 2 MiB, end markers inside chunks, dictionaries of 0 .. 3 bytes.  Valid streams at EXACT capacity."""
+    cases, exp = _directed_expectations()
+    _check_built(cases, exp, _emulate(cases, [max(len(e[1]), 1) if e[0] == 0 else len(e[1]) + 300 for e in exp]))
+
+
+def test_built_streams_one_byte_short_of_capacity():
+    cases, exp = _directed_expectations()
+    pick = [i for i, c in enumerate(cases) if c.status == 0 and len(c.plain) > 1 and
+            c.name.split("-")[0] in ("states", "copy", "every", "probabilities", "0x80", "4KiB", "raw", "properties", "end")]
+    assert len(pick) >= 30
+    res = _emulate([cases[i] for i in pick], [len(cases[i].plain) - 1 for i in pick])
+    for i, r in zip(pick, res):
+        assert r[0] == 901, "%s: status %d" % (cases[i].name, r[0])
+
+
+@pytest.mark.parametrize("seed", range(2))
+def test_built_streams_random(seed):
+    """Seeded random built streams, half of them restricted to what liblzma decodes, the other half drawn from everything the
+    reference accepts."""
+    import random
+    rnd = random.Random(0x12A4B00 + seed)
+    cases = [B.random_stream(rnd, rnd.choice([1, 9, 300, 4000, 20000]), i % 2 == 0) for i in range(100)]
+    exp = [O.lzma2(c.stream, c.dict_byte) if c.kind == "lzma2" else O.lzma_raw(c.stream, *c.props) for c in cases]
+    for i, (c, e) in enumerate(zip(cases, exp)):
+        assert e == (0, c.plain, c.consumed), "the builder and the oracle disagree on a stream it built (seed %d, stream %d)" % (seed, i)
+    _check_built(cases, exp, _emulate(cases, [max(len(c.plain), 1) for c in cases]), "seed %d, " % seed)
