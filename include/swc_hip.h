@@ -37,7 +37,7 @@ extern "C" {
  * ---------------------------------------------------------------------------------------------- */
 typedef enum swc_codec {
     SWC_CODEC_DEFLATE = 1, /* raw RFC 1951 stream      -- Deflate.decompress(_:)   Deflate.swift:30-249     */
-    SWC_CODEC_LZ4_BLOCK = 2, /* one LZ4 block           -- LZ4.process(block:_:)    LZ4.swift:332-413        */
+    SWC_CODEC_LZ4_BLOCK = 2, /* one LZ4 block           -- LZ4.process(block:_:)    LZ4.swift:332-413; aux: swc_lz4_aux below */
     SWC_CODEC_LZMA2 = 3,   /* raw LZMA2 chunk stream   -- LZMA2Decoder.decode()    LZMA2Decoder.swift:34-99 */
     SWC_CODEC_LZMA = 4,    /* raw LZMA1 stream         -- LZMADecoder.decode()     LZMADecoder.swift:107-284*/
     SWC_CODEC_BZIP2_BLOCK = 5, /* one bzip2 block body -- BZip2.decode(_:_:)       BZip2.swift:97-270       */
@@ -57,15 +57,42 @@ typedef enum swc_codec {
                               extension: the reference writes no dynamic block).  Where it is not dynamic, the bytes of 8  */
 } swc_codec;
 
+/* aux of an SWC_CODEC_LZ4_BLOCK job (0: an independent block, as ever).  With either bit the launch needs the workspace
+ * (SWC_E_NEED_WORKSPACE without one).
+ *   SWC_LZ4_LINKED (valid on job i > 0): the job CONTINUES job i - 1 of the array, as the dependent blocks of a frame do
+ *     (LZ4.swift:306-313).  A run of linked jobs behind an unlinked HEAD is a chain.  The engine sets
+ *     out = jobs[i-1].out + (the bytes of job i - 1 that exist: min(out_len, out_cap)) -- `out` is an OUT field of a linked job,
+ *     written back with the result -- and the job's history is the last min(65,536, bytes the chain has produced so far) bytes
+ *     in front of `out`, in place; while the chain has produced nothing, the head's adjacent prefix (below) is the history, and
+ *     not at all afterwards -- the reference's rule (`out.isEmpty`, LZ4.swift:307-312).
+ *     out_cap of every job stays the bound on its OWN output (for a frame: the maximum block size), so the head's buffer must
+ *     hold the SUM of the chain's out_cap.  dict must be NULL (else SWC_E_INVALID_ARGUMENT).  The head must be a job of the
+ *     two-phase path: linked jobs behind a head whose prefix is NOT adjacent (the lane kernel's job), and linked jobs with no
+ *     head in front of them (job 0 and what is linked to it), all report SWC_E_INVALID_ARGUMENT with out_len = in_consumed = 0;
+ *     that head itself is decoded as ever.  All blocks of all chains are parsed
+ *     in one launch; one wave then carries a chain's blocks through the copy in order.
+ *     A failed job of a chain keeps its own status, out_len and in_consumed (a match that reaches in front of the chain's
+ *     history: SWC_E_DATA_CORRUPTED with out_len = in_consumed = 0); every job behind it in the chain reports the same status
+ *     with out_len = in_consumed = 0.  The first error in order is the one the reference throws.
+ *   SWC_LZ4_STORED: `in` is not compressed: it is copied to `out`, out_len = in_consumed = in_len (SWC_E_CAPACITY, nothing
+ *     copied, where in_len > out_cap).  For the stored blocks of a chain, whose place nobody knows before the launch.
+ * A prefix that is ADJACENT (dict + dict_len == out), on a head or any unlinked job, is history in place as well: with the
+ * workspace the job takes the two-phase path (parse, wave copy) like a block without a prefix.  A prefix anywhere else is
+ * decoded by the one-block-per-lane kernel, as before. */
+typedef enum swc_lz4_aux {
+    SWC_LZ4_LINKED = 1,
+    SWC_LZ4_STORED = 2
+} swc_lz4_aux;
+
 typedef struct swc_job {
     const uint8_t* in;    /* device pointer to the unit's compressed bytes                           */
     uint64_t in_len;
-    uint8_t* out;         /* device pointer, caller allocated                                        */
+    uint8_t* out;         /* device pointer, caller allocated (OUT for an SWC_LZ4_LINKED job: set by the engine) */
     uint64_t out_cap;
     uint64_t out_len;     /* OUT: bytes produced; for SWC_E_CAPACITY on Deflate/LZ4: bytes required   */
     uint64_t in_consumed; /* OUT                                                                     */
     int32_t status;       /* OUT: swc_status                                                         */
-    int32_t aux;          /* IN : LZMA2 dictionary-size byte | LZMA props (lc | lp<<8 | pb<<16) | BZIP2: start bit (0..7) */
+    int32_t aux;          /* IN : LZMA2 dictionary-size byte | LZMA props (lc | lp<<8 | pb<<16) | BZIP2: start bit (0..7) | LZ4: swc_lz4_aux bits */
     const uint8_t* dict;  /* IN : LZ4 prefix dictionary (device) or NULL                             */
     uint64_t dict_len;    /* IN : LZ4 dictionary length | LZMA: uncompressed size (UINT64_MAX = unknown) | LZMA dict size in the high half, see swc_hip.h notes */
 } swc_job;
@@ -253,7 +280,9 @@ int swc_unarchive_many_devices(int kind, const uint8_t* const* archives, const s
  * points use internally, for callers that stage their data on the device themselves:
  *   kind 1  BGZF: every gzip member that carries the 'BC' extra field (GzipHeader.swift:110-156): offset / comp_len of its
  *           Deflate stream, uncomp_len = ISIZE.  SWC_E_INVALID_ARGUMENT if a member lacks the field.
- *   kind 4  LZ4 frame (LZ4.swift:278-299): the blocks of the frame the buffer opens with; aux = 1 for stored blocks.
+ *   kind 4  LZ4 frame (LZ4.swift:278-299): the blocks of the frame the buffer opens with; aux = 1 for stored blocks; flags
+ *           bit 0 = the block continues its predecessor (every block but the first of a frame with dependent blocks: a job
+ *           with SWC_LZ4_LINKED), 0 throughout a frame of independent blocks.
  *   kind 5  bzip2: every BIT offset of the 48-bit block magic (BZip2.swift:74-88) -- candidates, a magic may occur in data.
  *   kind 6  xz: the LZMA2-only blocks listed by the index of every stream (XZArchive.swift:132-192 read backwards):
  *           offset / comp_len of the LZMA2 data, uncomp_len, aux = dictionary-size byte.
@@ -269,7 +298,7 @@ typedef struct swc_block_ref {
     uint64_t comp_len;
     uint64_t uncomp_len;  /* 0 = not known from the framing */
     uint32_t aux;
-    uint32_t flags;       /* kind 7 only, else 0 */
+    uint32_t flags;       /* kinds 4 and 7 only, else 0 */
 } swc_block_ref;
 int swc_index_blocks(int kind, const uint8_t* in, size_t len, swc_block_ref* refs, size_t cap, size_t* n);
 

@@ -415,9 +415,10 @@ class SwcBlockRef(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("comp_len", C.c_uint64), ("uncomp_len", C.c_uint64), ("aux", C.c_uint32), ("flags", C.c_uint32)]
 
 
-def index_blocks(kind, data):
+def index_blocks(kind, data, flags=False):
     """Host block discovery (swc_index_blocks; no device needed).  kind: 'bgzf' | 'lz4' | 'bzip2' | 'xz' | 'lzma2'.
-    Returns [(offset, comp_len, uncomp_len, aux)] -- for 'lzma2' (offset, comp_len, uncomp_len, control byte, flags);
+    Returns [(offset, comp_len, uncomp_len, aux)] -- for 'lzma2', and for any kind with flags=True, (offset, comp_len,
+    uncomp_len, aux, flags): 'lz4' sets flags bit 0 on a block that continues its predecessor (a job with SWC_LZ4_LINKED);
     offsets are bytes from the start (bzip2: bits)."""
     kinds = {"bgzf": 1, "lz4": 4, "bzip2": 5, "xz": 6, "lzma2": 7}
     lib = _lib.load()
@@ -430,6 +431,6 @@ def index_blocks(kind, data):
     st = lib.swc_index_blocks(kinds[kind], data, len(data), refs, n.value, C.byref(n))
     if st:
         _raise(st)
-    if kind == "lzma2":
+    if kind == "lzma2" or flags:
         return [(r.offset, r.comp_len, r.uncomp_len, r.aux, r.flags) for r in refs[:n.value]]
     return [(r.offset, r.comp_len, r.uncomp_len, r.aux) for r in refs[:n.value]]

@@ -27,10 +27,16 @@ class DeviceBatch:
     addresses (inputs are replicated, every job owns its own output range), as SURVEY.md section 8d asks for:
     nothing is served from the 256 MiB Infinity Cache by accident."""
 
+    LZ4_LINKED, LZ4_STORED = 1, 2   # aux bits of an "lz4_block" job (include/swc_hip.h: swc_lz4_aux)
+
     def __init__(self, codec, units, caps, aux=None, extra=None, dict_values=None, tile=1, device="cuda:0", replicate_inputs=True,
-                 select=None):
+                 select=None, dicts=None, prefixes=None, guard=0):
         """select = (lo, hi): the jobs are the units lo..hi-1 of the TILED unit list (list entry i is distinct unit i % n_distinct
-        in replica i // n_distinct); default: the whole list of n_distinct * tile entries."""
+        in replica i // n_distinct); default: the whole list of n_distinct * tile entries.
+        LZ4 (tile = 1): dicts[i] = a prefix dictionary staged somewhere else (bytes or None); prefixes[i] = a prefix staged directly
+        in front of job i's output (an adjacent prefix: history in place).  The output ranges follow each other in job order, so
+        the head of a chain of LZ4_LINKED jobs owns the sum of the chain's capacities; guard = that many bytes of 0xA5 in front of
+        every unlinked job's range (and its prefix) and behind the last one -- unwritten_intact() checks them."""
         import torch
         self.torch = torch
         self.lib = _lib.load()
@@ -63,9 +69,21 @@ class DeviceBatch:
         for t in range(in_tiles):
             self.d_in[t * in_round:(t + 1) * in_round].copy_(h)
         out_each = out_sz[k_idx]
-        out_off = np.concatenate([[0], np.cumsum(out_each)[:-1]]).astype(np.uint64) if self.n else np.zeros(0, dtype=np.uint64)
-        out_total = int(out_each.sum())
+        self._guard = int(guard)
+        self._prefixes = None
+        if dicts is not None or prefixes is not None or guard:
+            assert tile == 1 and select is None
+            aux_l = [0] * nd if aux is None else [int(a) for a in aux]
+            front = np.array([(0 if aux_l[i] & self.LZ4_LINKED else int(guard)) + (_align(len(prefixes[i])) if prefixes is not None and prefixes[i] else 0)
+                              for i in range(nd)], dtype=np.uint64)
+            out_off = (np.concatenate([[0], np.cumsum(out_each + front)[:-1]]).astype(np.uint64) + front) if self.n else np.zeros(0, dtype=np.uint64)
+            out_total = int((out_each + front).sum()) + int(guard)
+        else:
+            out_off = np.concatenate([[0], np.cumsum(out_each)[:-1]]).astype(np.uint64) if self.n else np.zeros(0, dtype=np.uint64)
+            out_total = int(out_each.sum())
         self.d_out = torch.empty(out_total + 16, dtype=torch.uint8, device=self.device)
+        if guard:
+            self.d_out.fill_(0xA5)
         jobs = np.zeros(self.n, dtype=JOB_DTYPE)
         jobs["in"] = self.d_in.data_ptr() + ((t_idx - np.uint64(t0)) * np.uint64(in_round) if replicate_inputs else 0) + in_off[k_idx]
         jobs["in_len"] = lens[k_idx]
@@ -78,6 +96,23 @@ class DeviceBatch:
             jobs["dict_len"] = np.array(extra, dtype=np.uint64)[k_idx]
         if dict_values is not None:  # integer carried in the `dict` field (LZMA: dictionary size, BZip2: stored block CRC)
             jobs["dict"] = np.array(dict_values, dtype=np.uint64)[k_idx]
+        if dicts is not None and any(d is not None for d in dicts):   # prefixes somewhere else: one more input buffer
+            blob = b"".join(bytes(d) + bytes(_align(len(d)) - len(d)) for d in dicts if d is not None)
+            self.d_dicts = torch.from_numpy(np.frombuffer(blob + bytes(16), dtype=np.uint8).copy()).to(self.device)
+            at = 0
+            for i, d in enumerate(dicts):
+                if d is not None:
+                    jobs["dict"][i] = self.d_dicts.data_ptr() + at
+                    jobs["dict_len"][i] = len(d)
+                    at += _align(len(d))
+        if prefixes is not None:
+            self._prefixes = [None if p is None else bytes(p) for p in prefixes]
+            for i, p in enumerate(self._prefixes):
+                if p:
+                    o = int(out_off[i]) - len(p)
+                    self.d_out[o:o + len(p)].copy_(torch.from_numpy(np.frombuffer(p, dtype=np.uint8).copy()))
+                    jobs["dict"][i] = self.d_out.data_ptr() + o
+                    jobs["dict_len"][i] = len(p)
         self._out_off = out_off.astype(np.int64)
         self.unit_index = k_idx            # which distinct unit every job decodes
         self.caps = caps[k_idx]
@@ -174,11 +209,35 @@ class DeviceBatch:
         self.torch.cuda.synchronize(self.device)
         return self.d_jobs.cpu().numpy().view(JOB_DTYPE)
 
-    def output(self, i, n=None):
-        r = self.results() if n is None else None
+    def output(self, i, n=None, moved=False):
+        """The bytes job i left (n of them, default: as many as its record says).  moved=True: from where the job's `out` points
+        after the launch -- the engine sets the `out` of an LZ4_LINKED job -- instead of where the batch put it."""
+        r = self.results() if n is None or moved else None
         ln = int(min(r["out_len"][i], r["out_cap"][i])) if n is None else n
-        o = int(self._out_off[i])
+        o = int(r["out"][i]) - self.d_out.data_ptr() if moved else int(self._out_off[i])
+        if not 0 <= o <= self.d_out.numel() - 16 - ln:
+            raise RuntimeError("job %d: `out` points outside the batch's output buffer" % i)
         return self.d_out[o:o + ln].cpu().numpy().tobytes()
+
+    def out_offset(self, i):
+        """Where job i's `out` points after the launch, in bytes from where the batch put job i's own range."""
+        return int(self.results()["out"][i]) - self.d_out.data_ptr() - int(self._out_off[i])
+
+    def unwritten_intact(self):
+        """A batch built with guard != 0: every byte of the output buffer outside what the job records say was produced still
+        holds 0xA5, and every adjacent prefix its bytes."""
+        r = self.results()
+        blob = self.d_out.cpu().numpy()[:self.d_out.numel() - 16].copy()
+        ok = True
+        for i in range(self.n):
+            o = int(r["out"][i]) - self.d_out.data_ptr()
+            blob[o:o + int(min(r["out_len"][i], r["out_cap"][i]))] = 0xA5
+            p = self._prefixes[i] if self._prefixes is not None else None
+            if p:
+                po = int(self._out_off[i]) - len(p)
+                ok = ok and blob[po:po + len(p)].tobytes() == p
+                blob[po:po + len(p)] = 0xA5
+        return ok and bool((blob == 0xA5).all())
 
 
 def bgzf_workspace_bytes(n_bytes, block_size=65280):

@@ -21,6 +21,7 @@
 static_assert(sizeof(swc_job) == sizeof(swc::Job), "swc_job and swc::Job must have the same layout");
 static_assert(offsetof(swc_job, status) == offsetof(swc::Job, status), "layout");
 static_assert(offsetof(swc_job, dict_len) == offsetof(swc::Job, dict_len), "layout");
+static_assert(SWC_LZ4_LINKED == swc::kLz4Linked && SWC_LZ4_STORED == swc::kLz4Stored, "aux of an LZ4 block job");
 
 namespace swc {
 
@@ -293,8 +294,11 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
             in_off[k] = at + (sub ? (size_t)(u.in - u.base) : 0);
             dict_off[k] = in_total;
             if (u.dict) in_total += (u.dict_len + 15) & ~(size_t)15;
-            out_off[k] = out_total;
-            out_total += (cap[pending[k]] + 15) & ~(size_t)15;
+            // (an adjacent prefix lies in the output area, right in front of its unit's output; the outputs of a chain follow
+            // each other in list order: the head's room is the sum of the chain's capacities and more)
+            const size_t adj = u.dict && u.dict_adjacent ? (u.dict_len + 15) & ~(size_t)15 : 0;
+            out_off[k] = out_total + adj;
+            out_total += adj + ((cap[pending[k]] + 15) & ~(size_t)15);
         }
         // workspace: per-job areas (prefix-summed) where the codec sizes them from the capacity, else one size for all
         std::vector<uint64_t> ws_off;
@@ -351,12 +355,17 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
             j.in_consumed = 0;
             j.status = SWC_E_DEVICE;
             j.aux = u.aux;
-            j.dict = u.dict ? d_in + dict_off[k] : reinterpret_cast<const uint8_t*>((uintptr_t)u.dict_value);
+            j.dict = u.dict ? (u.dict_adjacent ? d_out + out_off[k] - u.dict_len : d_in + dict_off[k]) : reinterpret_cast<const uint8_t*>((uintptr_t)u.dict_value);
             j.dict_len = u.dict ? u.dict_len : u.extra;
         }
         if (!ws_off.empty()) memcpy(up + in_bytes + jobs_bytes, ws_off.data(), ws_off.size() * sizeof(uint64_t));
         tr.mark("stage inputs (pinned)", up_bytes);
         if (hipMemcpyAsync(d_in, up, up_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return SWC_E_DEVICE;
+        for (size_t k = 0; k < m; k++) {   // adjacent prefixes: from where they were staged to the front of their unit's output
+            const HostUnit& u = units[pending[k]];
+            if (u.dict && u.dict_adjacent && u.dict_len &&
+                hipMemcpyAsync(d_out + out_off[k] - u.dict_len, d_in + dict_off[k], u.dict_len, hipMemcpyDeviceToDevice, stream) != hipSuccess) return SWC_E_DEVICE;
+        }
         const uint64_t* d_off = !ws_off.empty() ? reinterpret_cast<const uint64_t*>(d_jobs + jobs_bytes) : nullptr;
         // Deflate units that want their CRC-32 (gzip members, ZIP entries): the copy kernel leaves it, as 32-bit words in the
         // first half of the checksum area (widened on the way down)
@@ -387,6 +396,18 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
         for (size_t k = 0; k < m; k++) {
             HostUnit& u = units[pending[k]];
             const Job& j = res[k];
+            if (u.chain) {   // final as it is; a linked unit's output lies where the launch put it
+                const size_t produced = (size_t)std::min<uint64_t>(j.out_len, j.out_cap);
+                const size_t at = (u.aux & SWC_LZ4_LINKED) ? (size_t)(j.out - d_out) : out_off[k];
+                if (j.out < d_out || at > out_total || produced > out_total - at) return SWC_E_DEVICE;
+                u.status = j.status;
+                u.aux_out = j.aux;
+                u.in_consumed = (size_t)j.in_consumed;
+                u.out_size = produced;
+                u.in_dst = u.dst != nullptr && produced <= u.dst_cap;
+                done.push_back(CopyOut{&u, outs + at, produced});
+                continue;
+            }
             if (j.status == SWC_E_NEED_WORKSPACE && !want_ws) {
                 next.push_back(pending[k]);
                 continue;

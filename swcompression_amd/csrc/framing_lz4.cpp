@@ -1,11 +1,13 @@
 // framing_lz4.cpp -- host side of LZ4: frame / legacy-frame / skippable-frame parsing and block
-// discovery feeding ONE batched launch per frame (independent blocks) -- the reference decodes the
-// blocks one after another on the CPU.
+// discovery feeding ONE batched launch per frame -- independent blocks as independent jobs, dependent
+// (linked) blocks as one chain of SWC_LZ4_LINKED jobs -- where the reference decodes the blocks one
+// after another on the CPU.
 //   LZ4.decompress(data:dictionary:dictionaryID:)   reference Sources/LZ4/LZ4.swift:73-91
 //   LZ4.multiDecompress                              :116-146
 //   process(skippableFrame:) :148-155   process(legacyFrame:) :160-186   process(frame:_:_:) :188-330
 // Errors are reported in STREAM ORDER exactly as the sequential reference would meet them: framing
 // checks of block k only count once every block before k has decoded cleanly.
+#include <algorithm>
 #include <vector>
 #include "framing.h"
 
@@ -165,17 +167,73 @@ int frame_tail(const uint8_t* p, size_t n, const FrameInfo& fi, const std::vecto
     return SWC_OK;
 }
 
+// Dependent blocks: block k references the last 64 KiB the frame has produced so far (:306-313).  Units for ALL blocks of the
+// frame, stored ones included, as one chain: the head, then SWC_LZ4_LINKED jobs, which the launch writes back to back
+// (include/swc_hip.h).  The first block's prefix -- the last 64 KiB of the dictionary (:307-309) -- goes in front of the output.
+// A unit's capacity is the maximum block size, or what its compressed bytes can decode to at most where that is less (a stored
+// block: its length; a compressed one: 255 bytes per byte, what a length byte adds) -- a frame of many short blocks does not ask
+// for n x 4 MiB.  The declared content size is not used to cut capacities: where the blocks lie is known only after the launch,
+// and a legal frame with short blocks in the middle would be sent to the block-by-block path for nothing.
+void linked_units(const uint8_t* base, const FrameInfo& fi, const uint8_t* dict, size_t dict_len, bool have_dict, std::vector<HostUnit>& units) {
+    const size_t nb = fi.blocks.size();
+    for (size_t k = 0; k < nb; k++) {
+        const BlockRef& b = fi.blocks[k];
+        HostUnit u;
+        u.in = base + b.off;
+        u.in_len = b.len;
+        u.cap_hint = std::max<size_t>(1, (size_t)std::min<uint64_t>(fi.max_block, b.compressed ? (uint64_t)b.len * 255u + 64u : (uint64_t)b.len));
+        u.cap_exact = true;
+        u.chain = true;
+        u.aux = (k ? SWC_LZ4_LINKED : 0) | (b.compressed ? 0 : SWC_LZ4_STORED);
+        if (k == 0 && have_dict) {
+            const size_t dl = dict_len > 65536 ? 65536 : dict_len;
+            u.dict = dict_len ? dict + (dict_len - dl) : reinterpret_cast<const uint8_t*>("");
+            u.dict_len = dl;
+            u.dict_adjacent = true;
+        }
+        units.push_back(std::move(u));
+    }
+}
+// Appends the outputs of the chain `units` (one per block of `fi`) to `out`.  Returns the first decode error in stream order;
+// `again`: a unit wanted more room than the chain gave it (a block that decodes to more than the frame's maximum block size,
+// which the reference does not enforce; more records than the workspace was sized for) -- nothing was appended, the
+// block-by-block path decides.
+int linked_append(const FrameInfo& fi, const HostUnit* units, std::vector<uint8_t>& out, bool& again) {
+    again = false;
+    const size_t start = out.size();
+    for (size_t k = 0; k < fi.blocks.size(); k++) {
+        const HostUnit& u = units[k];
+        if (u.status == SWC_E_CAPACITY || u.status == SWC_E_NEED_WORKSPACE) { out.resize(start); again = true; return SWC_OK; }
+        if (u.status) return u.status;
+        out.insert(out.end(), u.out.begin(), u.out.end());
+    }
+    return SWC_OK;
+}
+
 int frame(const uint8_t* p, size_t n, const uint8_t* dict, size_t dict_len, bool have_dict, int64_t ext_dict_id,
-          std::vector<uint8_t>& out, size_t& adv) {
+          std::vector<uint8_t>& out, size_t& adv, bool chain = true) {
     FrameInfo fi;
     int st = frame_parse(p, n, have_dict, ext_dict_id, fi);
     if (st) return st;
     const size_t start = out.size();
+    bool again = !chain;
     if (fi.independent) {
         st = decode_independent(p, fi.blocks, dict, dict_len, have_dict, fi.max_block, out);  // :305
         if (st) return st;
-    } else {
-        // Dependent blocks: block k references the last 64 KiB produced so far (:306-313) -- a serial chain.
+    } else if (chain) {
+        // one upload of the frame, ONE launch, one download
+        std::vector<HostUnit> units;
+        units.reserve(fi.blocks.size());
+        linked_units(p, fi, dict, dict_len, have_dict, units);
+        if (!units.empty()) {
+            st = run_units(SWC_CODEC_LZ4_BLOCK, units);
+            if (st) return st;
+        }
+        st = linked_append(fi, units.data(), out, again);
+        if (st) return st;
+    }
+    if (!fi.independent && again) {
+        // Block by block, each with its window uploaded as a dictionary: a chain that wanted more room than it had.
         for (const BlockRef& b : fi.blocks) {
             if (!b.compressed) { out.insert(out.end(), p + b.off, p + b.off + b.len); continue; }
             HostUnit u;
@@ -213,8 +271,8 @@ int skippable(const uint8_t* p, size_t n, size_t& adv) {                        
 
 }  // namespace
 
-// ---- many-archive batching (swc_unarchive_many): an archive that opens with a standard frame of independent blocks
-// contributes its blocks to a shared launch; everything else (skippable / legacy / dependent frames) is not batchable.
+// ---- many-archive batching (swc_unarchive_many): an archive that opens with a standard frame contributes its blocks to a
+// shared launch -- independent blocks as they are, dependent blocks as a chain; skippable and legacy frames are not batchable.
 struct Lz4Plan::Impl { FrameInfo fi; };
 Lz4Plan::Lz4Plan() : impl(new Impl) {}
 Lz4Plan::~Lz4Plan() { delete impl; }
@@ -222,14 +280,25 @@ bool lz4_plan_prepare(const uint8_t* in, size_t n, Lz4Plan& plan, std::vector<Ho
     if (n < 4 || le32(in) != 0x184D2204u) return false;
     plan.early_status = frame_parse(in + 4, n - 4, false, -1, plan.impl->fi);
     if (plan.early_status) return true;                       // header error: final, no units
-    if (!plan.impl->fi.independent) return false;
     plan.first_unit = units.size();
-    independent_units(in + 4, plan.impl->fi.blocks, nullptr, 0, false, plan.impl->fi.max_block, units);
+    if (plan.impl->fi.independent) independent_units(in + 4, plan.impl->fi.blocks, nullptr, 0, false, plan.impl->fi.max_block, units);
+    else linked_units(in + 4, plan.impl->fi, nullptr, 0, false, units);   // a chain: the chains of many frames share the launch, a wave each
     return true;
 }
 int lz4_plan_finish(const uint8_t* in, size_t n, const Lz4Plan& plan, const std::vector<HostUnit>& units, std::vector<uint8_t>& res) {
     if (plan.early_status) return plan.early_status;
-    int st = independent_append(in + 4, plan.impl->fi.blocks, units.data() + plan.first_unit, res);
+    int st;
+    if (plan.impl->fi.independent) st = independent_append(in + 4, plan.impl->fi.blocks, units.data() + plan.first_unit, res);
+    else {
+        bool again = false;
+        st = linked_append(plan.impl->fi, units.data() + plan.first_unit, res, again);
+        if (again) {   // (a chain that wanted more room: the frame once more, block by block)
+            size_t adv = 0;
+            st = frame(in + 4, n - 4, nullptr, 0, false, -1, res, adv, false);
+            if (st != SWC_OK && st != SWC_E_DATA_CHECKSUM_MISMATCH) res.clear();
+            return st;
+        }
+    }
     if (st) { res.clear(); return st; }
     size_t adv = 0;
     st = frame_tail(in + 4, n - 4, plan.impl->fi, res, 0, adv);
@@ -242,7 +311,8 @@ bool lz4_frame_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& 
     if (in_len < 4 || le32(in) != 0x184D2204u) return false;
     FrameInfo fi;
     if (frame_parse(in + 4, in_len - 4, false, -1, fi) != SWC_OK) return false;
-    for (const BlockRef& b : fi.blocks) out.push_back({(uint64_t)b.off + 4, (uint64_t)b.len, 0, b.compressed ? 0u : 1u});
+    for (const BlockRef& b : fi.blocks)   // flags bit 0: the block continues its predecessor (a job with SWC_LZ4_LINKED)
+        out.push_back({(uint64_t)b.off + 4, (uint64_t)b.len, 0, b.compressed ? 0u : 1u, !fi.independent && &b != &fi.blocks.front() ? 1u : 0u});
     return true;
 }
 
@@ -375,8 +445,8 @@ int swc_lz4_compress(const uint8_t* data, size_t len, int independent_blocks, in
 }
 
 // All frames of a multi-frame buffer in one launch: block sizes are in the block headers, so the frames (standard frames
-// with independent blocks, skippable frames) can be walked without decoding anything.  Used only if every frame then passes
-// its own checks; anything else -- dependent blocks, legacy frames, a dictionary, any error -- goes to the sequential loop
+// of independent or of dependent blocks, skippable frames) can be walked without decoding anything.  Used only if every frame then
+// passes its own checks; anything else -- legacy frames, a dictionary, any error -- goes to the sequential loop
 // below, which alone defines errors and partial results (LZ4.swift:116-146).
 static bool lz4_multi_batched(const uint8_t* in, size_t in_len, std::vector<uint8_t>& all, std::vector<size_t>& sz) {
     struct Fr { size_t at; FrameInfo fi; size_t first_unit; };
@@ -396,9 +466,10 @@ static bool lz4_multi_batched(const uint8_t* in, size_t in_len, std::vector<uint
         frames.emplace_back();
         Fr& f = frames.back();
         f.at = pos + 4;
-        if (frame_parse(in + f.at, in_len - f.at, false, -1, f.fi) != SWC_OK || !f.fi.independent || f.fi.framing != SWC_OK) return false;
+        if (frame_parse(in + f.at, in_len - f.at, false, -1, f.fi) != SWC_OK || f.fi.framing != SWC_OK) return false;
         f.first_unit = units.size();
-        independent_units(in + f.at, f.fi.blocks, nullptr, 0, false, f.fi.max_block, units);
+        if (f.fi.independent) independent_units(in + f.at, f.fi.blocks, nullptr, 0, false, f.fi.max_block, units);
+        else linked_units(in + f.at, f.fi, nullptr, 0, false, units);
         pos = f.at + f.fi.off + (f.fi.content_checksum ? 4 : 0);
         if (pos > in_len) return false;
     }
@@ -406,7 +477,9 @@ static bool lz4_multi_batched(const uint8_t* in, size_t in_len, std::vector<uint
     if (!units.empty() && run_units(SWC_CODEC_LZ4_BLOCK, units) != SWC_OK) return false;
     for (const Fr& f : frames) {
         const size_t start = all.size();
-        if (independent_append(in + f.at, f.fi.blocks, units.data() + f.first_unit, all) != SWC_OK) return false;
+        bool again = false;
+        if (f.fi.independent) { if (independent_append(in + f.at, f.fi.blocks, units.data() + f.first_unit, all) != SWC_OK) return false; }
+        else if (linked_append(f.fi, units.data() + f.first_unit, all, again) != SWC_OK || again) return false;
         size_t adv = 0;
         std::vector<uint8_t> one(all.begin() + (std::ptrdiff_t)start, all.end());
         if (frame_tail(in + f.at, in_len - f.at, f.fi, one, 0, adv) != SWC_OK) return false;

@@ -93,7 +93,7 @@ int many_single_unit(int kind, const uint8_t* const* archives, const size_t* len
     return SWC_OK;
 }
 
-// kind 4: LZ4.decompress(data:) per archive; archives that open with a frame of independent blocks share one launch
+// kind 4: LZ4.decompress(data:) per archive; archives that open with a standard frame share one launch (dependent blocks as chains)
 int many_lz4(const uint8_t* const* archives, const size_t* lens, size_t n, std::vector<Result>& res) {
     std::vector<HostUnit> units;
     std::vector<std::unique_ptr<Lz4Plan>> plans(n);
@@ -108,7 +108,7 @@ int many_lz4(const uint8_t* const* archives, const size_t* lens, size_t n, std::
     for (size_t i = 0; i < n; i++) {
         if (plans[i]) {
             res[i].status = lz4_plan_finish(archives[i], lens[i], *plans[i], units, res[i].data);
-        } else {   // skippable / legacy / dependent-block frames: the single-archive path
+        } else {   // skippable / legacy frames: the single-archive path
             uint8_t* o = nullptr;
             size_t ol = 0, used = 0;
             res[i].status = swc_lz4_decompress(archives[i], lens[i], nullptr, 0, -1, &o, &ol, &used);

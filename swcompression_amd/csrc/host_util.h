@@ -71,6 +71,12 @@ struct HostUnit {
     int32_t aux = 0;
     const uint8_t* dict = nullptr;
     size_t dict_len = 0;
+    // LZ4: the prefix is staged directly in front of the unit's output, so that it is history in place (swc_hip.h: an adjacent prefix)
+    bool dict_adjacent = false;
+    // LZ4: the unit is part of a chain (its head, or a unit with SWC_LZ4_LINKED right behind its predecessor in the list).  The
+    // runner lays the outputs of a chain out back to back and never launches one of its units again on its own: a status that
+    // would otherwise mean "once more with more room" (SWC_E_CAPACITY, SWC_E_NEED_WORKSPACE) is the caller's to act on.
+    bool chain = false;
     uint64_t extra = 0;          // codec specific (goes to Job::dict_len when dict == nullptr)
     uint64_t dict_value = 0;     // codec specific integer carried in Job::dict when dict == nullptr (LZMA: dictionary size)
     // Optional: where the output is wanted (a place inside the caller's final buffer, `dst_cap` bytes of room).  If the

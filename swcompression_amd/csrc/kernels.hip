@@ -4,8 +4,9 @@
 // each codec maps a unit to the piece of the machine its serial part needs:
 //   Deflate   phase 1 one stream per WAVEFRONT, 64 sub-chunks decoded at once (self-synchronising Huffman decode);
 //             phase 2 (LZ77 resolve) one stream per WORKGROUP, byte cells in LDS   inflate_sync.h, inflate_lane.h, lz_resolve.h
-//   LZ4       parse one block per wavefront (64 sub-chunks at once), then the same resolve kernel; dictionary blocks per lane
-//                                                                                                lz4_wave.h, lz4_lane.h
+//   LZ4       parse one block per wavefront (64 sub-chunks at once), then the same resolve kernel; linked blocks parsed in parallel
+//             and copied as a chain by one wavefront; blocks with a dictionary somewhere else per lane
+//                                                                                   lz4_wave.h, lz4_chain.h, lz4_lane.h
 //   LZMA      one stream per wavefront, probability model in LDS                                               lzma_wave.h
 //   BZip2     Huffman + MTF per wavefront, counting-sort scatter per wavefront, inverse BWT by all lanes of a wavefront over
 //             a cut cycle, block CRC per workgroup                                                           bzip2_block.h
@@ -23,6 +24,7 @@
 #include "lz_copy.h"
 #include "lz4_lane.h"
 #include "lz4_wave.h"
+#include "lz4_chain.h"
 #include "lz4_comp.h"
 #include "deflate_comp.h"
 #include "lzma_wave.h"
@@ -75,12 +77,25 @@ __device__ __forceinline__ uint32_t order_class(uint64_t len) {
 }
 // (one LDS histogram per workgroup and one global atomic per class it holds: 100,000 members of ONE size class otherwise meet at
 // one counter -- 2 ms for the two kernels, a tenth of the launch they were meant to shorten)
+// CHAINS (LZ4 decode launches): the wave of a chain's head carries the whole chain through the copy (lz4_chain.h), so a HEAD is
+// ordered by the compressed bytes of its chain -- up to kOrderChainMax jobs of it: the class saturates long before -- and the
+// chains stay intact whatever the order: the walk goes by job index.  A linked job keeps the class of its own size, which is what
+// the parse, where every job is a wave's work, wants; in the copy its wave ends at once, wherever it stands in the list.
+constexpr uint32_t kOrderChainMax = 4096;
+template <bool CHAINS>
+__device__ __forceinline__ uint64_t order_len(const Job* __restrict__ jobs, uint32_t g, uint32_t n) {
+    uint64_t len = jobs[g].in_len;
+    if (CHAINS && (jobs[g].aux & kLz4Linked) == 0)
+        for (uint32_t j = g + 1u; j < n && j - g <= kOrderChainMax && (jobs[j].aux & kLz4Linked) != 0; j++) len += jobs[j].in_len;
+    return len;
+}
+template <bool CHAINS>
 __global__ __launch_bounds__(256) void swc_order_hist_kernel(const Job* __restrict__ jobs, uint32_t n, uint32_t* __restrict__ hist) {
     __shared__ uint32_t cnt[kOrderClasses];
     const uint32_t t = threadIdx.x, g = blockIdx.x * 256u + t;
     cnt[t] = 0;
     __syncthreads();
-    if (g < n) atomicAdd(&cnt[order_class(jobs[g].in_len)], 1u);
+    if (g < n) atomicAdd(&cnt[order_class(order_len<CHAINS>(jobs, g, n))], 1u);
     __syncthreads();
     if (cnt[t]) atomicAdd(&hist[t], cnt[t]);
 }
@@ -93,12 +108,13 @@ __global__ __launch_bounds__(kOrderClasses) void swc_order_prefix_kernel(uint32_
     for (uint32_t i = 0; i < t; i++) a += s[i];
     hist[t] = a;
 }
+template <bool CHAINS>
 __global__ __launch_bounds__(256) void swc_order_scatter_kernel(const Job* __restrict__ jobs, uint32_t n, uint32_t* __restrict__ cursor, uint32_t* __restrict__ perm) {
     __shared__ uint32_t cnt[kOrderClasses], base[kOrderClasses];
     const uint32_t t = threadIdx.x, g = blockIdx.x * 256u + t;
     cnt[t] = 0;
     __syncthreads();
-    const uint32_t c = g < n ? order_class(jobs[g].in_len) : 0u;
+    const uint32_t c = g < n ? order_class(order_len<CHAINS>(jobs, g, n)) : 0u;
     const uint32_t r = g < n ? atomicAdd(&cnt[c], 1u) : 0u;      // my rank among the group's members of the class
     __syncthreads();
     if (cnt[t]) base[t] = atomicAdd(&cursor[t], cnt[t]);          // the group's slots of class t
@@ -106,7 +122,7 @@ __global__ __launch_bounds__(256) void swc_order_scatter_kernel(const Job* __res
     if (g < n) perm[base[c] + r] = g;
 }
 // device buffer of the calling thread for the order of one launch on `stream` (perm[n] | cursors), or nullptr
-static const uint32_t* job_order(const Job* jobs, size_t n, hipStream_t stream) {
+static const uint32_t* job_order(const Job* jobs, size_t n, hipStream_t stream, bool chains = false) {
     if (n < kOrderMin) return nullptr;
     struct Buf { hipStream_t s; int dev; uint32_t* p; size_t cap; };
     static thread_local std::vector<Buf> bufs;   // (never freed: a few hundred KB per launching thread and stream)
@@ -126,9 +142,11 @@ static const uint32_t* job_order(const Job* jobs, size_t n, hipStream_t stream) 
     uint32_t* cursor = b->p + n;
     if (hipMemsetAsync(cursor, 0, kOrderClasses * sizeof(uint32_t), stream) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     const dim3 grid((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(swc_order_hist_kernel, grid, dim3(256), 0, stream, jobs, (uint32_t)n, cursor);
+    if (chains) hipLaunchKernelGGL(swc_order_hist_kernel<true>, grid, dim3(256), 0, stream, jobs, (uint32_t)n, cursor);
+    else hipLaunchKernelGGL(swc_order_hist_kernel<false>, grid, dim3(256), 0, stream, jobs, (uint32_t)n, cursor);
     hipLaunchKernelGGL(swc_order_prefix_kernel, dim3(1), dim3(kOrderClasses), 0, stream, cursor);
-    hipLaunchKernelGGL(swc_order_scatter_kernel, grid, dim3(256), 0, stream, jobs, (uint32_t)n, cursor, b->p);
+    if (chains) hipLaunchKernelGGL(swc_order_scatter_kernel<true>, grid, dim3(256), 0, stream, jobs, (uint32_t)n, cursor, b->p);
+    else hipLaunchKernelGGL(swc_order_scatter_kernel<false>, grid, dim3(256), 0, stream, jobs, (uint32_t)n, cursor, b->p);
     return b->p;
 }
 __device__ __forceinline__ uint32_t job_of(const uint32_t* order, uint32_t b, uint32_t n) { return order ? order[b] : xcd_job(b, n); }
@@ -212,8 +230,15 @@ __device__ __forceinline__ void lz_copy_body(const Job* __restrict__ jobs, uint3
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZC_WAVES, SWC_LZC_WAVES))) void swc_lz_copy_kernel(const Job* __restrict__ jobs, uint32_t n, WsMap wm, const uint32_t* __restrict__ order) {
     lz_copy_body<lzc::CfgDeflate>(jobs, n, wm, order);
 }
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZC4_WAVES, SWC_LZC4_WAVES))) void swc_lz4_copy_kernel(const Job* __restrict__ jobs, uint32_t n, WsMap wm, const uint32_t* __restrict__ order) {
-    lz_copy_body<lzc::CfgLz4, SWC_LZ4_RECORD_MODE>(jobs, n, wm, order);   // (the literals come from the block itself)
+// LZ4: the wave of a job takes the linked jobs behind it along, one after the other (lz4_chain.h); it writes their `out` and their
+// results, so the job list is not read-only here.  only_chain: the launch's other jobs are swc_lz4_resolve_kernel's.
+__device__ __forceinline__ int32_t lz4_next_aux(const Job* jobs, uint32_t g, uint32_t n) { return g + 1u < n ? jobs[g + 1u].aux : 0; }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZC4_WAVES, SWC_LZC4_WAVES))) void swc_lz4_copy_kernel(Job* jobs, uint32_t n, WsMap wm, const uint32_t* __restrict__ order, int only_chain) {
+    __shared__ __attribute__((aligned(16))) lzc::Lds<lzc::CfgLz4::kWin> lds;
+    uint32_t g = job_of(order, blockIdx.x, n);
+    if (g >= n) return;
+    if (only_chain && !lz4w::chain_job(jobs[g], lz4_next_aux(jobs, g, n))) return;
+    lz4w::copy_chain<lzc::CfgLz4, SWC_LZ4_RECORD_MODE>(jobs, g, n, wm, &lds);   // (the literals come from the block itself)
 }
 // The Deflate copy kernel that ends with the stream's CRC-32: the same body, the same window, the same 24 waves per CU.  A kernel
 // of its own, so that swc_lz_copy_kernel keeps its instructions and its 40 VGPRs (the tail holds four rows of the stream in flight).
@@ -233,9 +258,8 @@ static bool wave_copier(size_t n) {
     const int c = g_lz_copier;
     return c < 0 || (c == 1 && n >= kCopierMin);   // (tuning value -1: the wave kernel whatever the batch size)
 }
-static void launch_lz_copy(bool lz4, const Job* jobs, size_t n, const WsMap& wm, const uint32_t* order, hipStream_t stream) {
-    if (lz4) hipLaunchKernelGGL(swc_lz4_copy_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, jobs, (uint32_t)n, wm, order);
-    else hipLaunchKernelGGL(swc_lz_copy_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, jobs, (uint32_t)n, wm, order);
+static void launch_lz_copy(const Job* jobs, size_t n, const WsMap& wm, const uint32_t* order, hipStream_t stream) {
+    hipLaunchKernelGGL(swc_lz_copy_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, jobs, (uint32_t)n, wm, order);
 }
 
 // Optional per-kernel timing of the calling thread's last batch launch (bench.py: roofline per kernel).  HIP events on the
@@ -286,7 +310,7 @@ static void launch_inflate_phase2(Job* jobs, size_t n, const WsMap& wm, const ui
             launch_crc32_group(jobs, n, crcs, stream);
             return;
         }
-        launch_lz_copy(false, jobs, n, wm, order, stream);
+        launch_lz_copy(jobs, n, wm, order, stream);
         g_pt.mark(stream);
         return;
     }
@@ -333,13 +357,21 @@ hipError_t launch_inflate(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStr
 // Blocks without a dictionary prefix take the two-phase path: one block per wavefront for the sequence parse
 // (lz4_wave.h), then the LZ77 resolve kernel of lz_resolve.h in the Deflate configuration (one block per 512-thread
 // workgroup, 64 KiB ring with 32 KiB of history, two workgroups per CU; match bytes from further back come from the
-// output buffer).  Blocks with a dictionary prefix (dependent frames, external dictionaries) stay on the
-// one-block-per-lane decoder (lz4_lane.h).  Each kernel skips the jobs of the other kind.
+// output buffer).  Blocks with a dictionary prefix that does not lie in place in front of their output (external dictionaries)
+// stay on the one-block-per-lane decoder (lz4_lane.h).  Jobs with HISTORY in place -- the linked blocks of a dependent frame, an
+// adjacent prefix -- and stored jobs take the record-mode parse and the wave copier, a chain of linked jobs on one wave
+// (lz4_chain.h).  Each kernel skips the jobs of the other kinds.
 __global__ __launch_bounds__(64) void swc_lz4_lane_kernel(Job* __restrict__ jobs, uint32_t n, int only_dict) {
     uint32_t g = blockIdx.x * kWave + threadIdx.x;
     if (g >= n) return;
     Job job = jobs[g];
-    if (only_dict && job.dict == nullptr) return;
+    if (only_dict) {
+        if (!lz4w::lane_job(job)) return;
+    } else if ((job.aux & (kLz4Linked | kLz4Stored)) != 0) {   // (no workspace: nowhere to leave the records of a chain)
+        job.status = SWC_E_NEED_WORKSPACE; job.out_len = 0; job.in_consumed = 0;
+        put_result(jobs, g, job);
+        return;
+    }
     lz4::lz4_block_job(job);
     put_result(jobs, g, job);
 }
@@ -348,15 +380,20 @@ __global__ __launch_bounds__(64) void swc_lz4_lane_kernel(Job* __restrict__ jobs
 #define SWC_LZ4_PARSE_WAVES 4
 #endif
 // R8: eight-byte records that say where their literals lie in the block, no literal stream (for the wave copy kernel);
-// otherwise the records and the dense literal stream swc_lz4_resolve_kernel reads
+// otherwise the records and the dense literal stream swc_lz4_resolve_kernel reads.
+// which: 0 = every job that is not the lane decoder's, 1 = only the jobs of lz4w::chain_job (chains, stored blocks, adjacent
+// prefixes: always RM != 0 and the wave copier), 2 = only the others.
 template <int RM>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZ4_PARSE_WAVES))) void swc_lz4_parse_kernel(Job* __restrict__ jobs, uint32_t n, WsMap wm, uint64_t* prof, const uint32_t* __restrict__ order) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZ4_PARSE_WAVES))) void swc_lz4_parse_kernel(Job* __restrict__ jobs, uint32_t n, WsMap wm, uint64_t* prof, const uint32_t* __restrict__ order, int which) {
     uint32_t g = job_of(order, blockIdx.x, n);
     if (g >= n) return;
     Job job = jobs[g];
-    if (job.dict != nullptr) return;
+    if (lz4w::lane_job(job)) return;
+    if (which != 0 && lz4w::chain_job(job, lz4_next_aux(jobs, g, n)) != (which == 1)) return;
     __shared__ __attribute__((aligned(16))) uint8_t stage[lz4w::kStageLds];
-    lz4w::lz4_parse_job<kWave, RM>(job, wm.area(g), wm.bytes(g), (int)threadIdx.x, stage, prof ? prof + 32 * (size_t)g : nullptr);
+    uint64_t hist = 0;
+    if (RM == 0 || !lz4w::parse_preset(job, hist))
+        lz4w::lz4_parse_job<kWave, RM>(job, wm.area(g), wm.bytes(g), (int)threadIdx.x, stage, prof ? prof + 32 * (size_t)g : nullptr, RM == 0 ? 0u : hist);
     if (threadIdx.x == 0) put_result(jobs, g, job);
 }
 
@@ -365,7 +402,7 @@ __global__ __launch_bounds__(lz4w::kResolveThreads) __attribute__((amdgpu_waves_
     uint32_t g = job_of(order, blockIdx.x, n);
     if (g >= n) return;
     Job job = jobs[g];
-    if (job.dict != nullptr) return;
+    if (lz4w::lane_job(job) || lz4w::chain_job(job, lz4_next_aux(jobs, g, n))) return;
     lzr::resolve_job<lz4w::kResolveThreads, lz4w::kRingLog2, lz4w::kKeep, true>(job, wm.area(g), wm.bytes(g), &lds, prof ? prof + 32 * (size_t)g + 16 : nullptr);
 }
 
@@ -383,16 +420,21 @@ hipError_t launch_lz4(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStream_
     // The parse is latency bound per block (a serial chase), so all blocks are parsed in ONE launch: the more waves
     // in flight, the better the latency hides (8,192 blocks = 8 waves per SIMD).
     g_pt.begin(stream);
-    const uint32_t* order = job_order(jobs, n, stream);
+    const uint32_t* order = job_order(jobs, n, stream, true);   // (a head by its chain's bytes)
     hipLaunchKernelGGL(swc_lz4_lane_kernel, grid, block, 0, stream, jobs, (uint32_t)n, 1);
     g_pt.mark(stream);
     const WsMap wm{(uint8_t*)ws, stride, ws_off};
+    // Below kCopierMin the chains, stored blocks and adjacent prefixes of the launch still take the record-mode parse and the wave
+    // copier -- the byte-cell resolver knows no history -- and each kernel skips the other's jobs.
     const bool copier = wave_copier(n);
-    if (copier) hipLaunchKernelGGL(swc_lz4_parse_kernel<SWC_LZ4_RECORD_MODE>, dim3((unsigned)n), block, 0, stream, jobs, (uint32_t)n, wm, g_prof, order);
-    else hipLaunchKernelGGL(swc_lz4_parse_kernel<0>, dim3((unsigned)n), block, 0, stream, jobs, (uint32_t)n, wm, g_prof, order);
+    if (copier) hipLaunchKernelGGL(swc_lz4_parse_kernel<SWC_LZ4_RECORD_MODE>, dim3((unsigned)n), block, 0, stream, jobs, (uint32_t)n, wm, g_prof, order, 0);
+    else {
+        hipLaunchKernelGGL(swc_lz4_parse_kernel<0>, dim3((unsigned)n), block, 0, stream, jobs, (uint32_t)n, wm, g_prof, order, 2);
+        hipLaunchKernelGGL(swc_lz4_parse_kernel<SWC_LZ4_RECORD_MODE>, dim3((unsigned)n), block, 0, stream, jobs, (uint32_t)n, wm, g_prof, order, 1);
+    }
     g_pt.mark(stream);
-    if (copier) launch_lz_copy(true, jobs, n, wm, order, stream);
-    else hipLaunchKernelGGL(swc_lz4_resolve_kernel, dim3((unsigned)n), dim3(lz4w::kResolveThreads), 0, stream, jobs, (uint32_t)n, wm, g_prof, order);
+    if (!copier) hipLaunchKernelGGL(swc_lz4_resolve_kernel, dim3((unsigned)n), dim3(lz4w::kResolveThreads), 0, stream, jobs, (uint32_t)n, wm, g_prof, order);
+    hipLaunchKernelGGL(swc_lz4_copy_kernel, dim3((unsigned)n), block, 0, stream, jobs, (uint32_t)n, wm, order, copier ? 0 : 1);
     g_pt.mark(stream);
     return hipGetLastError();
 }

@@ -132,6 +132,12 @@ struct Parser {
     uint64_t ip, pos, nlit, sequences;
     int64_t last_match_start;
     uint32_t nrec;
+    // History in front of the block (LZ4.swift:334: `out` starts as the prefix): an adjacent prefix's length, or -- a linked job,
+    // whose history is known only to the chain walk of lz_copy.h -- 65,536, which no offset exceeds.  `reach`: the furthest a
+    // match of the block reaches in front of it (the largest offset - position where that is positive); the chain walk compares
+    // it with the history that came to be.
+    uint64_t hist = 0;
+    uint32_t reach = 0;
 #if defined(SWC_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
     uint64_t pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // cycles: 0 staging, 1 count passes, 2 scans, 3 emit, 4 checked steps; 5 rounds, 6 passes
     uint64_t tlast = 0;
@@ -284,7 +290,8 @@ struct Parser {
         if (n - ip < 2) { emit(lit, 0, 0, lit_at); pos += lit; return SWC_E_DATA_TRUNCATED; }   // :378
         const uint32_t offset = rd(ip) | (rd(ip + 1) << 8);
         ip += 2;
-        if (!(offset > 0 && offset <= produced)) { emit(lit, 0, 0, lit_at); pos += lit; return SWC_E_DATA_CORRUPTED; }  // :382
+        if (!(offset > 0 && offset <= produced + hist)) { emit(lit, 0, 0, lit_at); pos += lit; return SWC_E_DATA_CORRUPTED; }  // :382
+        if (offset > produced && offset - produced > reach) reach = (uint32_t)(offset - produced);
         uint64_t mlen = 4 + (token & 0xF);
         if (mlen == 19) {
             for (;;) {
@@ -650,11 +657,21 @@ struct Parser {
             if (pos + tot_out > cap || (uint64_t)nrec + tot_rec > max_rec) return;   // the capacity / the workspace: the checked step counts on
             // :382 every offset must reach back no further than the bytes produced in front of its match
             SIMT_BEGIN(t, N)
-                const uint64_t p0 = pos + (x_out[t] - c_out[t]);
+                const uint64_t p0 = pos + (x_out[t] - c_out[t]) + hist;
                 const int32_t room = p0 > 0x40000000ull ? 0x40000000 : (int32_t)p0;
                 pb[t] = (uint32_t)t < nv && c_rec[t] != 0 && (int32_t)c_need[t] > room;
             SIMT_END
             if (simt::wave_ballot<N>(pb)) return;                             // an offset beyond the output: the checked step reports it
+            if (hist != 0) {   // how far the round's matches reach in front of the block
+                PT<uint32_t, N> rr;
+                SIMT_BEGIN(t, N)
+                    const int64_t d = (int64_t)(int32_t)c_need[t] - (int64_t)(pos + (x_out[t] - c_out[t]));
+                    rr[t] = (uint32_t)t < nv && c_rec[t] != 0 && d > 0 ? (uint32_t)d : 0u;
+                SIMT_END
+                simt::wave_scan_max_incl<N>(rr);
+                const uint32_t r = simt::wave_read<N>(rr, N - 1);
+                if (r > reach) reach = r;
+            }
             if (R4) {   // the sequences of a round follow the copier's rule among themselves: an anchor only if its running sum does not stand at the round's first sequence
                 if (s_pred != ip) anchor(nrec, ip);
             }
@@ -699,9 +716,33 @@ struct Parser {
     }
 };
 
-// One wavefront = one job (blocks WITHOUT a dictionary prefix; those with one stay on lz4_lane.h).
+// ---- which path does a job take?  (include/swc_hip.h: the contract of SWC_CODEC_LZ4_BLOCK) ------------------------------------
+// A prefix that ends where the output begins is history in place: the two-phase path reads it like earlier output.
+SWC_HD bool adjacent_prefix(const Job& j) { return j.dict != nullptr && j.dict + j.dict_len == j.out; }
+// the one-block-per-lane decoder: a prefix somewhere else
+SWC_HD bool lane_job(const Job& j) { return j.dict != nullptr && (j.aux & (kLz4Linked | kLz4Stored)) == 0 && !adjacent_prefix(j); }
+// `next_aux`: the aux of the job behind it in the array (0 for the last).  Chains, stored jobs and adjacent prefixes always take
+// the parse in record mode SWC_LZ4_RECORD_MODE and the wave copier (lz_copy.h: copy_chain), whatever the size of the launch.
+SWC_HD bool chain_job(const Job& j, int32_t next_aux) {
+    return (j.aux & (kLz4Linked | kLz4Stored)) != 0 || (next_aux & kLz4Linked) != 0 || adjacent_prefix(j);
+}
+// What the parse launch leaves for a job that has nothing to parse; false: parse it (with `hist` bytes of history).
+SWC_HD bool parse_preset(Job& job, uint64_t& hist) {
+    hist = 0;
+    if ((job.aux & kLz4Linked) && job.dict != nullptr) { job.status = SWC_E_INVALID_ARGUMENT; job.out_len = 0; job.in_consumed = 0; return true; }
+    if (job.aux & kLz4Stored) {
+        job.status = job.in_len > job.out_cap ? SWC_E_CAPACITY : SWC_OK;
+        job.out_len = job.in_len;
+        job.in_consumed = job.in_len;
+        return true;
+    }
+    hist = (job.aux & kLz4Linked) ? 65536u : job.dict != nullptr ? job.dict_len : 0u;
+    return false;
+}
+
+// One wavefront = one job (blocks whose prefix is not in place stay on lz4_lane.h).
 template <int W, int RM = 0>
-SWC_D void lz4_parse_job(Job& job, uint8_t* ws, size_t ws_bytes, int lane, uint8_t* stage, uint64_t* prof = nullptr) {
+SWC_D void lz4_parse_job(Job& job, uint8_t* ws, size_t ws_bytes, int lane, uint8_t* stage, uint64_t* prof = nullptr, uint64_t hist = 0) {
     constexpr bool R8 = RM == 1, R4 = RM == 2;
     Parser<W, RM> ps;
     ps.lane = lane;
@@ -719,6 +760,7 @@ SWC_D void lz4_parse_job(Job& job, uint8_t* ws, size_t ws_bytes, int lane, uint8
     ps.ip = ps.pos = ps.nlit = ps.sequences = 0;
     ps.last_match_start = -1;
     ps.nrec = 0;
+    ps.hist = hist;
     const size_t lo = ws ? lzr::lit_offset(ws_bytes, job.out_cap) : 0;
     ps.recs = (SWC_AS_GLOBAL uint32_t*)(ws + sizeof(lzr::StreamHeader));
     size_t rec_end = lo;   // the wave's scratch rows sit between the record list and the literal stream, if the area has room for them
@@ -764,7 +806,7 @@ SWC_D void lz4_parse_job(Job& job, uint8_t* ws, size_t ws_bytes, int lane, uint8
             SWC_AS_GLOBAL lzr::StreamHeader* h = (SWC_AS_GLOBAL lzr::StreamHeader*)ws;
             h->nrec = ps.nrec;
             h->pad0 = R4 ? ps.nanc : 0u;   // (R4: the number of anchors)
-            h->nlit = ps.nlit;
+            h->nlit = RM != 0 ? ps.nlit | ((uint64_t)ps.reach << 32) : ps.nlit;   // (RM != 0: the literals stay in the block, fewer than 2^32 of them; the upper half is `reach`)
         }
     }
     job.out_len = ps.pos;

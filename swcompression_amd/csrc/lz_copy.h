@@ -161,6 +161,13 @@ struct Copier {
     gptr out;
     gcptr lits;        // the stream's dense literal stream (16-byte aligned base); R8: the compressed block
     P limit;           // bytes of `out` that exist: min(bytes produced, capacity)
+    // INP: HISTORY in front of the stream (an LZ4 block's adjacent prefix, the earlier blocks of its chain).  `out` is where the
+    // history begins and the stream's own bytes begin at position `start`: a match that reaches in front of the block is an
+    // ordinary FAR source, and no position is negative.  Everything below `start` was written, and has arrived, before run().
+    P start = 0;
+    static constexpr uint32_t kSeam = 528;   // bytes of history run() fetches into the window: more than a far read of a match piece (kMaxLen, dword steps) overshoots
+    static_assert(kSeam >= lzr::kMaxLen + 16u && kSeam % 16u == 0u && kSeam + 16u + kSpanMax <= WIN, "the seam");
+    SWC_D P vlo() const { return INP ? (P)A + start : (P)A; }   // the lowest virtual position that is this stream's to write
     uint32_t nin;      // R8: bytes of `lits` that exist (the block's compressed size: nothing is read beyond it)
 
     // wave state (the same in every lane)
@@ -195,7 +202,8 @@ struct Copier {
             const uint32_t w0 = (uint32_t)(f0 - vbase);
             const uint32_t nchunk = (uint32_t)((v16 - f0) >> 4);
             gptr ob = obase + f0;
-            const bool whole = f0 >= A && v16 <= vlim;          // (all but the first and the last flush of a stream)
+            const P lo = vlo();                                 // (the 16 bytes around it are shared with whatever lies in front: the history, a neighbour's buffer)
+            const bool whole = f0 >= lo && v16 <= vlim;         // (all but the first and the last flush of a stream)
             if (whole) {
                 SIMT_BEGIN(t, W)
 #pragma unroll 1
@@ -206,11 +214,11 @@ struct Copier {
 #pragma unroll 1
                     for (uint32_t c = (uint32_t)t; c < nchunk; c += (uint32_t)W) {
                         const P cv = f0 + (P)(16u * c);
-                        if (cv >= A && cv + 16u <= vlim) {
+                        if (cv >= lo && cv + 16u <= vlim) {
                             lzr::store_16(ob + 16u * c, *(const u128*)(l->win + w0 + 16u * c));
                         } else {   // the first chunk of an unaligned output, the chunk the limit cuts
                             for (uint32_t e = 0; e < 16u; e++)
-                                if (cv + e >= A && cv + e < vlim) ob[16u * c + e] = l->win[w0 + 16u * c + e];
+                                if (cv + e >= lo && cv + e < vlim) ob[16u * c + e] = l->win[w0 + 16u * c + e];
                         }
                     }
                 SIMT_END_WAVE
@@ -219,10 +227,10 @@ struct Copier {
         }
         if (final && vend > fv) {
             const uint32_t ntail = (uint32_t)(vend - fv);   // < 16
-            const P f0 = fv;
+            const P f0 = fv, lo = vlo();
             const uint32_t w0 = (uint32_t)(f0 - vbase);
             SIMT_BEGIN(t, W)
-                if ((uint32_t)t < ntail && f0 + (uint32_t)t >= A && f0 + (uint32_t)t < vlim) obase[f0 + (uint32_t)t] = l->win[w0 + (uint32_t)t];
+                if ((uint32_t)t < ntail && f0 + (uint32_t)t >= lo && f0 + (uint32_t)t < vlim) obase[f0 + (uint32_t)t] = l->win[w0 + (uint32_t)t];
             SIMT_END_WAVE
         }
     }
@@ -702,7 +710,8 @@ struct Copier {
 
     // a stream of a few bytes: one lane builds it in the window, byte by byte (the prefetches of run() read eight bytes that exist)
     SWC_D void tiny(const SWC_AS_GLOBAL uint32_t* recs, uint32_t nrec) {
-        const uint32_t lim = (uint32_t)limit;   // < 64
+        const P st = INP ? start : (P)0;
+        const uint32_t lim = (uint32_t)(limit - st);   // < 64
         SIMT_BEGIN(t, W)
             if (t == 0) {
                 uint32_t pos = 0, ai = 0;
@@ -717,12 +726,13 @@ struct Copier {
                         S += seq_bytes(li, le);
                     }
                     for (uint32_t k = 0; k < li && pos < lim; k++, pos++, lp++) l->win[pos] = lits[lp];
-                    for (uint32_t k = 0; k < le && pos < lim; k++, pos++) l->win[pos] = pos >= di ? l->win[pos - di] : (uint8_t)0;
+                    for (uint32_t k = 0; k < le && pos < lim; k++, pos++)
+                        l->win[pos] = pos >= di ? l->win[pos - di] : INP && st + pos >= di ? (uint8_t)out[st + pos - di] /* the history */ : (uint8_t)0;
                 }
             }
         SIMT_END_WAVE
         SIMT_BEGIN(t, W)
-            if ((uint32_t)t < lim) out[t] = l->win[t];
+            if ((uint32_t)t < lim) out[st + (uint32_t)t] = l->win[t];
         SIMT_END_WAVE
     }
 
@@ -733,8 +743,26 @@ struct Copier {
         fv = 0;
         landed = 0;
         if (nrec == 0) return;
-        if (limit < 64u) { tiny(recs, nrec); return; }
-        P rpos = 0;                      // output bytes finished by earlier groups
+        const P st = INP ? start : (P)0;
+        if (limit - st < 64u) { tiny(recs, nrec); return; }
+        if (INP && st != 0) {
+            // The window starts with the last bytes of the history, from HBM: the stream's first 16-byte line shares them, and a
+            // far read that begins in front of the window may run a few bytes into it -- into bytes that are in HBM already.
+            const P vs = (P)A + st;
+            vbase = (vs - (st < kSeam ? st : (P)kSeam)) & ~(P)15;
+            fv = landed = vs & ~(P)15;
+            const uint32_t npre = (uint32_t)(vs - vbase);
+            gcptr hb = (gcptr)(out - A) + vbase;                          // (16-byte aligned)
+            const P vb = vbase;
+            const uint32_t a = A;
+            SIMT_BEGIN(t, W)
+                for (uint32_t o = 16u * (uint32_t)t; o < npre; o += 16u * (uint32_t)W) {
+                    if (vb + o >= a && o + 16u <= npre) *(u128*)(l->win + o) = lzr::load_16(hb + o);
+                    else for (uint32_t e = 0; e < 16u; e++) if (vb + o + e >= a && o + e < npre) l->win[o + e] = hb[o + e];
+                }
+            SIMT_END_WAVE
+        }
+        P rpos = st;                     // output bytes finished by earlier groups (and the history in front of them)
         uint32_t base = 0;               // first record of the group
         PT<uint32_t, W> r_nx, o_nx;      // the records of the group after `nxt` (R8: and their literal offsets), on their way
         Group cur, nxt;
@@ -752,7 +780,7 @@ struct Copier {
         };
         load_records(0);
         if (R4) { anc_i = 0; next_anchor(); }
-        front(nxt, r_nx, o_nx, nrec, 0, 0, ~(P)0, 0u);
+        front(nxt, r_nx, o_nx, nrec, st, 0, ~(P)0, 0u);
         load_records(nxt.ntake);
         bool more = true;
         while (more) {
@@ -821,18 +849,20 @@ using CfgLz4 = Cfg<SWC_LZC4_WIN, SWC_LZC4_SPAN, SWC_LZC4_KEEP, SWC_LZC4_LITP>;
 // One job: `ws` is the stream's workspace area of `area` bytes written by phase 1.  RM 1 (R8) / 2 (R4), LZ4: the literals are
 // fetched from the job's input; R8: the area holds the header and eight-byte records; R4: four-byte records, and the anchors where
 // the literal stream would be (their number in the header's pad0).
+// `hist` (RM != 0): bytes of history that lie in place in front of job.out (Copier::start).
 template <typename CFG, int RM = 0>
-SWC_D void copy_job(const Job& job, const uint8_t* ws, size_t area, Lds<CFG::kWin>* lds) {
+SWC_D void copy_job(const Job& job, const uint8_t* ws, size_t area, Lds<CFG::kWin>* lds, uint32_t hist = 0) {
     const SWC_AS_GLOBAL lzr::StreamHeader* h = (const SWC_AS_GLOBAL lzr::StreamHeader*)ws;
     const size_t lo = lzr::lit_offset(area, job.out_cap);
     if (lo == 0) return;   // no literal stream: phase 1 reported SWC_E_NEED_WORKSPACE for this job
-    const uint64_t limit = job.out_len < job.out_cap ? job.out_len : job.out_cap;
+    const uint64_t limit = (job.out_len < job.out_cap ? job.out_len : job.out_cap) + (RM != 0 ? hist : 0u);
     const SWC_AS_GLOBAL uint32_t* recs = (const SWC_AS_GLOBAL uint32_t*)(ws + sizeof(lzr::StreamHeader));
     gcptr lits = RM != 0 ? (gcptr)job.in : (gcptr)ws + lo;
     if (limit < 0xFFF00000ull) {   // (positions, watermarks and their differences in 32 bits)
         Copier<CFG, uint32_t, RM> cp;
         cp.l = lds;
-        cp.out = (gptr)job.out;
+        cp.out = (gptr)job.out - (RM != 0 ? hist : 0u);
+        cp.start = RM != 0 ? hist : 0u;
         cp.lits = lits;
         cp.nin = RM != 0 ? (uint32_t)job.in_len : 0xFFFFFFFFu;   // (blocks are addressed with 32-bit offsets: the parse rejects larger ones)
         if (RM == 2) { cp.anc = (const SWC_AS_GLOBAL uint32_t*)(ws + lo); cp.nanc = h->pad0; }
@@ -841,7 +871,8 @@ SWC_D void copy_job(const Job& job, const uint8_t* ws, size_t area, Lds<CFG::kWi
     } else {
         Copier<CFG, uint64_t, RM> cp;
         cp.l = lds;
-        cp.out = (gptr)job.out;
+        cp.out = (gptr)job.out - (RM != 0 ? hist : 0u);
+        cp.start = RM != 0 ? hist : 0u;
         cp.lits = lits;
         cp.nin = RM != 0 ? (uint32_t)job.in_len : 0xFFFFFFFFu;
         if (RM == 2) { cp.anc = (const SWC_AS_GLOBAL uint32_t*)(ws + lo); cp.nanc = h->pad0; }

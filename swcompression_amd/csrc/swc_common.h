@@ -50,6 +50,9 @@ struct Job {
     uint64_t dict_len;     // LZ4: dictionary length; LZMA: declared uncompressed size (or ~0 = unknown)
 };
 
+// aux of an LZ4 block job (include/swc_hip.h: SWC_LZ4_LINKED, SWC_LZ4_STORED)
+constexpr int32_t kLz4Linked = 1, kLz4Stored = 2;
+
 // A kernel's results back to its entry of the job list (AUX: `aux` too -- bzip2's block CRC)
 template <bool AUX = false>
 SWC_D void put_result(Job* jobs, uint32_t g, const Job& job) {
