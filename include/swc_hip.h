@@ -36,7 +36,7 @@ extern "C" {
  * (HBM-resident input and output); the job array itself is in device memory too.
  * ---------------------------------------------------------------------------------------------- */
 typedef enum swc_codec {
-    SWC_CODEC_DEFLATE = 1, /* raw RFC 1951 stream      -- Deflate.decompress(_:)   Deflate.swift:30-249     */
+    SWC_CODEC_DEFLATE = 1, /* raw RFC 1951 stream      -- Deflate.decompress(_:)   Deflate.swift:30-249; aux: swc_deflate_aux below */
     SWC_CODEC_LZ4_BLOCK = 2, /* one LZ4 block           -- LZ4.process(block:_:)    LZ4.swift:332-413; aux: swc_lz4_aux below */
     SWC_CODEC_LZMA2 = 3,   /* raw LZMA2 chunk stream   -- LZMA2Decoder.decode()    LZMA2Decoder.swift:34-99 */
     SWC_CODEC_LZMA = 4,    /* raw LZMA1 stream         -- LZMADecoder.decode()     LZMADecoder.swift:107-284*/
@@ -84,15 +84,38 @@ typedef enum swc_lz4_aux {
     SWC_LZ4_STORED = 2
 } swc_lz4_aux;
 
+/* aux of an SWC_CODEC_DEFLATE job (0: one whole stream, as ever): the UNITS of a stream that was cut at its flush points.  An
+ * empty stored block ends with 00 00 FF FF on a byte boundary and the next block starts on the next byte, so the bytes between
+ * two such markers decode on their own -- as long as they refer to nothing in front of themselves (Z_FULL_FLUSH, pigz -i, this
+ * library's own segmented encoder).
+ *   SWC_DEFLATE_OPEN: the unit may end without a final block.  When the block loop (Deflate.swift:33-44) is about to read a block
+ *     header and the reader stands exactly at bit 8 * in_len, the job ends with SWC_OK and in_consumed = in_len.  At any other
+ *     position the job behaves like any other (fewer than three bits left: SWC_E_REF_TRAP).  aux is an OUT field too, as for
+ *     bzip2: the bit stays set where the unit ended open and is cleared otherwise -- a unit that met a final block ends there
+ *     like any stream.  in_len = 0 keeps its status.
+ *   SWC_DEFLATE_JOINED (valid on job i > 0): the engine sets out = jobs[i-1].out + min(out_len, out_cap) of job i - 1 -- `out` is
+ *     an OUT field, as with SWC_LZ4_LINKED.  A head and the joined jobs behind it are a RUN; the head's buffer must hold the SUM
+ *     of the run's out_cap, every out_cap still bounds its job's own output and workspace.  No history is shared: a distance
+ *     that reaches in front of the unit's own first byte is SWC_E_REF_TRAP, as ever; every job keeps its own status; a failed or
+ *     over-capacity job still occupies min(out_len, out_cap) bytes, and the jobs behind it are placed and decoded normally.
+ *     Joined jobs with no head in front of them -- job 0 and what is joined to it -- report SWC_E_INVALID_ARGUMENT with
+ *     out_len = in_consumed = 0.
+ * All units of all runs are parsed in one launch; between the parse and the copy one wavefront per 64 jobs places the joined ones
+ * (csrc/deflate_place.h), and the copy kernels write every unit byte-exact at whatever address it got. */
+typedef enum swc_deflate_aux {
+    SWC_DEFLATE_JOINED = 1,
+    SWC_DEFLATE_OPEN = 2
+} swc_deflate_aux;
+
 typedef struct swc_job {
     const uint8_t* in;    /* device pointer to the unit's compressed bytes                           */
     uint64_t in_len;
-    uint8_t* out;         /* device pointer, caller allocated (OUT for an SWC_LZ4_LINKED job: set by the engine) */
+    uint8_t* out;         /* device pointer, caller allocated (OUT for an SWC_LZ4_LINKED / SWC_DEFLATE_JOINED job: set by the engine) */
     uint64_t out_cap;
     uint64_t out_len;     /* OUT: bytes produced; for SWC_E_CAPACITY on Deflate/LZ4: bytes required   */
     uint64_t in_consumed; /* OUT                                                                     */
     int32_t status;       /* OUT: swc_status                                                         */
-    int32_t aux;          /* IN : LZMA2 dictionary-size byte | LZMA props (lc | lp<<8 | pb<<16) | BZIP2: start bit (0..7) | LZ4: swc_lz4_aux bits */
+    int32_t aux;          /* IN : LZMA2 dictionary-size byte | LZMA props (lc | lp<<8 | pb<<16) | BZIP2: start bit (0..7) | LZ4: swc_lz4_aux bits | Deflate: swc_deflate_aux bits (OUT as well) */
     const uint8_t* dict;  /* IN : LZ4 prefix dictionary (device) or NULL                             */
     uint64_t dict_len;    /* IN : LZ4 dictionary length | LZMA: uncompressed size (UINT64_MAX = unknown) | LZMA dict size in the high half, see swc_hip.h notes */
 } swc_job;
@@ -280,6 +303,12 @@ int swc_unarchive_many_devices(int kind, const uint8_t* const* archives, const s
  * points use internally, for callers that stage their data on the device themselves:
  *   kind 1  BGZF: every gzip member that carries the 'BC' extra field (GzipHeader.swift:110-156): offset / comp_len of its
  *           Deflate stream, uncomp_len = ISIZE.  SWC_E_INVALID_ARGUMENT if a member lacks the field.
+ *   kind 3  raw Deflate: the units the stream can be cut into -- a cut behind every 00 00 FF FF (the end of an empty stored block),
+ *           cuts merged until every unit but the last holds at least "deflate_unit_bytes" (swc_set_tuning; 0: one unit), no cut
+ *           at the very end of the buffer.  aux = the swc_deflate_aux bits of the unit's job (all but the first JOINED, all but
+ *           the last OPEN).  The markers are candidates -- they occur in stored data and in codes: a caller checks the result
+ *           as the single-shot calls do (every unit in front of some unit k SWC_OK, still OPEN, in_consumed == in_len; unit k
+ *           SWC_OK with the bit cleared) and decodes the stream whole otherwise.
  *   kind 4  LZ4 frame (LZ4.swift:278-299): the blocks of the frame the buffer opens with; aux = 1 for stored blocks; flags
  *           bit 0 = the block continues its predecessor (every block but the first of a frame with dependent blocks: a job
  *           with SWC_LZ4_LINKED), 0 throughout a frame of independent blocks.
@@ -353,6 +382,9 @@ int swc_7z_unpack_folders(swc_7z_folder* folders, size_t n);
 /* checksums used by the framing layer (CheckSums.swift:12-57, XxHash32.swift:24-83, Sha256.swift:28-142) */
 uint32_t swc_crc32(const uint8_t* p, size_t n, uint32_t prev);
 uint32_t swc_adler32(const uint8_t* p, size_t n);
+/* the sum of A ++ B from the sums of A and B and the length of B (the units of a Deflate run are summed one by one on the device) */
+uint32_t swc_crc32_combine(uint32_t a, uint32_t b, size_t len_b);
+uint32_t swc_adler32_combine(uint32_t a, uint32_t b, size_t len_b);
 uint64_t swc_crc64(const uint8_t* p, size_t n);
 uint32_t swc_bzip2_crc32(const uint8_t* p, size_t n);
 uint32_t swc_xxh32(const uint8_t* p, size_t n, uint32_t seed);
@@ -391,6 +423,11 @@ const char* swc_version(void);
  *                               the RLE1 undo -- as kernels of their own that walk out of the XCDs' L2 (csrc/bzip2_team.h)
  *                               unless the launch is tiny (1, default), never (0: one wavefront takes a block through all
  *                               stages), or always (2);
+ *   "deflate_unit_bytes" = n >= 0   process-wide: the Deflate decoders (swc_deflate_decompress, swc_gzip_unarchive,
+ *                               swc_gzip_multi_unarchive, swc_zlib_unarchive, swc_unarchive_many kinds 1-3) cut a stream behind the
+ *                               empty stored blocks it holds into units of at least n compressed bytes that decode in parallel in
+ *                               one launch (32768 is the value the tests and tools/exp_deflate_units.py use); a stream whose units do not stand alone is decoded whole afterwards
+ *                               (swc_stat "deflate_unit_fallbacks"); 0 (default, until the gain is measured: DESIGN.md 4.1.1): never cut;
  *   "bgzf_round_members" = 1..16384   process-wide, for tests: members per round of swc_bgzf_archive (default 16384); the file is
  *                               the same bytes whatever the round size. */
 int swc_set_tuning(const char* key, int value);
@@ -406,7 +443,8 @@ int swc_last_phase_ms(float* ms, int cap);
 
 /* Process-wide launch statistics of the host framing layer (monotonic, for tests and tuning): "launches" = batched
  * launches issued by the single-shot / many-archive entry points, "units" = units decoded by them, "xz_cache_hits" =
- * .xz blocks the sequential walk took from the index-driven ahead-of-time batch.  Unknown key: -1. */
+ * .xz blocks the sequential walk took from the index-driven ahead-of-time batch, "deflate_unit_fallbacks" = Deflate streams that
+ * were cut into units and had to be decoded whole after all.  Unknown key: -1. */
 long long swc_stat(const char* key);
 
 #ifdef __cplusplus

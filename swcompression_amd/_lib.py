@@ -100,6 +100,8 @@ def load():
         C.POINTER(C.c_int32))
     sig("swc_crc32", C.c_uint32, C.c_char_p, C.c_size_t, C.c_uint32)
     sig("swc_adler32", C.c_uint32, C.c_char_p, C.c_size_t)
+    sig("swc_crc32_combine", C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t)
+    sig("swc_adler32_combine", C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t)
     sig("swc_crc64", C.c_uint64, C.c_char_p, C.c_size_t)
     sig("swc_bzip2_crc32", C.c_uint32, C.c_char_p, C.c_size_t)
     sig("swc_xxh32", C.c_uint32, C.c_char_p, C.c_size_t, C.c_uint32)

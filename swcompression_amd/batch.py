@@ -28,6 +28,7 @@ class DeviceBatch:
     nothing is served from the 256 MiB Infinity Cache by accident."""
 
     LZ4_LINKED, LZ4_STORED = 1, 2   # aux bits of an "lz4_block" job (include/swc_hip.h: swc_lz4_aux)
+    DEFLATE_JOINED, DEFLATE_OPEN = 1, 2   # aux bits of a "deflate" job (swc_deflate_aux): the units of a stream cut at its flush points
 
     def __init__(self, codec, units, caps, aux=None, extra=None, dict_values=None, tile=1, device="cuda:0", replicate_inputs=True,
                  select=None, dicts=None, prefixes=None, guard=0):
@@ -35,7 +36,7 @@ class DeviceBatch:
         in replica i // n_distinct); default: the whole list of n_distinct * tile entries.
         LZ4 (tile = 1): dicts[i] = a prefix dictionary staged somewhere else (bytes or None); prefixes[i] = a prefix staged directly
         in front of job i's output (an adjacent prefix: history in place).  The output ranges follow each other in job order, so
-        the head of a chain of LZ4_LINKED jobs owns the sum of the chain's capacities; guard = that many bytes of 0xA5 in front of
+        the head of a chain of LZ4_LINKED jobs -- of a run of DEFLATE_JOINED jobs -- owns the sum of the chain's capacities; guard = that many bytes of 0xA5 in front of
         every unlinked job's range (and its prefix) and behind the last one -- unwritten_intact() checks them."""
         import torch
         self.torch = torch
@@ -211,7 +212,7 @@ class DeviceBatch:
 
     def output(self, i, n=None, moved=False):
         """The bytes job i left (n of them, default: as many as its record says).  moved=True: from where the job's `out` points
-        after the launch -- the engine sets the `out` of an LZ4_LINKED job -- instead of where the batch put it."""
+        after the launch -- the engine sets the `out` of an LZ4_LINKED / DEFLATE_JOINED job -- instead of where the batch put it."""
         r = self.results() if n is None or moved else None
         ln = int(min(r["out_len"][i], r["out_cap"][i])) if n is None else n
         o = int(r["out"][i]) - self.d_out.data_ptr() if moved else int(self._out_off[i])

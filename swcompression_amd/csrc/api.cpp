@@ -22,6 +22,7 @@ static_assert(sizeof(swc_job) == sizeof(swc::Job), "swc_job and swc::Job must ha
 static_assert(offsetof(swc_job, status) == offsetof(swc::Job, status), "layout");
 static_assert(offsetof(swc_job, dict_len) == offsetof(swc::Job, dict_len), "layout");
 static_assert(SWC_LZ4_LINKED == swc::kLz4Linked && SWC_LZ4_STORED == swc::kLz4Stored, "aux of an LZ4 block job");
+static_assert(SWC_DEFLATE_JOINED == swc::kDeflateJoined && SWC_DEFLATE_OPEN == swc::kDeflateOpen, "aux of a Deflate job");
 
 namespace swc {
 
@@ -152,8 +153,8 @@ void host_result_free(void* p) {
     free(p);
 }
 
-static std::atomic<long long> g_stats[3];
-void stat_add(int which, long long v) { if (which >= 0 && which < 3) g_stats[which] += v; }
+static std::atomic<long long> g_stats[4];
+void stat_add(int which, long long v) { if (which >= 0 && which < 4) g_stats[which] += v; }
 
 // What a thread keeps page-locked between calls, per direction.  Pinning is the expensive part of a large single-shot call
 // (a 268 MB result: tens of milliseconds to lock against 5 ms to copy), so a buffer that served an archive of a gigabyte
@@ -396,6 +397,40 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
         for (size_t k = 0; k < m; k++) {
             HostUnit& u = units[pending[k]];
             const Job& j = res[k];
+            if (u.chain && codec == SWC_CODEC_DEFLATE) {
+                // A run of units cut from ONE stream (framing_deflate.cpp), head first: the launch has laid their outputs out back to
+                // back, so what the stream decodes to is one range of the staging buffer.  It stands -- and is copied out, once, as the
+                // head's output -- if the units up to some unit kk ended open at their last byte and unit kk met a final block; the
+                // caller decides about anything else (the exact sizes of a run that lacked room are in `need`).
+                if (u.run_len == 0) continue;   // (a joined unit: its head has dealt with it)
+                if (u.run_len > m - k) return SWC_E_DEVICE;
+                size_t total = 0, kk = u.run_len;
+                bool placed = true;
+                for (size_t r = 0; r < u.run_len; r++) {
+                    HostUnit& v = units[pending[k + r]];
+                    const Job& jr = res[k + r];
+                    const size_t produced = (size_t)std::min<uint64_t>(jr.out_len, jr.out_cap);
+                    v.status = jr.status;
+                    v.aux_out = jr.aux;
+                    v.in_consumed = (size_t)jr.in_consumed;
+                    v.need = jr.out_len;
+                    v.out_size = produced;
+                    if (sum_kind && v.sum_kind == sum_kind) { v.sum = fused_crc ? reinterpret_cast<const uint32_t*>(sums)[k + r] : sums[k + r]; v.sum_valid = true; }
+                    if (kk != u.run_len) continue;
+                    placed = placed && jr.out == d_out + out_off[k] + total;
+                    total += produced;
+                    if (!(jr.status == SWC_OK && (jr.aux & SWC_DEFLATE_OPEN) != 0 && jr.in_consumed == jr.in_len)) kk = r;
+                }
+                u.run_used = kk;
+                u.run_ok = kk < u.run_len && placed && units[pending[k + kk]].status == SWC_OK && (units[pending[k + kk]].aux_out & SWC_DEFLATE_OPEN) == 0 &&
+                           total <= out_total - out_off[k];
+                u.run_bytes = u.run_ok ? total : 0;
+                if (u.run_ok) {
+                    u.in_dst = u.dst != nullptr && total <= u.dst_cap;
+                    done.push_back(CopyOut{&u, outs + out_off[k], total});
+                }
+                continue;
+            }
             if (u.chain) {   // final as it is; a linked unit's output lies where the launch put it
                 const size_t produced = (size_t)std::min<uint64_t>(j.out_len, j.out_cap);
                 const size_t at = (u.aux & SWC_LZ4_LINKED) ? (size_t)(j.out - d_out) : out_off[k];
@@ -472,6 +507,7 @@ int swc_set_tuning(const char* key, int value) try {
     if (!strcmp(key, "bzip2_hot_cxx") && (value == 0 || value == 1)) { set_bzip2_hot_cxx(value); return SWC_OK; }
     if (!strcmp(key, "bzip2_team_walk") && value >= 0 && value <= 2) { set_bzip2_team_walk(value); return SWC_OK; }
     if (!strcmp(key, "bgzf_round_members") && value >= 1 && value <= 16384) { set_bgzf_round_members(value); return SWC_OK; }
+    if (!strcmp(key, "deflate_unit_bytes") && value >= 0) { set_deflate_unit_bytes(value); return SWC_OK; }
     if (!strcmp(key, "pinned_keep_mib") && value >= 0) { g_pinned_keep = (size_t)value << 20; return SWC_OK; }
     if (!strcmp(key, "result_cache_mib") && value >= 0) { g_result_cache = (size_t)value << 20; return SWC_OK; }
     if (!strcmp(key, "pool_keep_mib") && value >= 0) {   // applies to the current device at once, to the others when they are first used
@@ -496,6 +532,7 @@ long long swc_stat(const char* key) {
     if (!strcmp(key, "launches")) return g_stats[0].load();
     if (!strcmp(key, "units")) return g_stats[1].load();
     if (!strcmp(key, "xz_cache_hits")) return g_stats[2].load();
+    if (!strcmp(key, "deflate_unit_fallbacks")) return g_stats[3].load();
     return -1;
 }
 

@@ -92,6 +92,33 @@ uint32_t swc_adler32(const uint8_t* p, size_t n) {
     return (b << 16) | a;
 }
 
+// a * b mod P over GF(2), both in the reflected form the CRC registers have (bit 31 = x^0)
+static uint32_t crc32_mulmod(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+    for (uint32_t m = 1u << 31; m != 0 && a != 0; m >>= 1) {
+        if (a & m) { p ^= b; a &= ~m; }
+        b = (b >> 1) ^ (0xEDB88320u & (0u - (b & 1u)));
+    }
+    return p;
+}
+// CRC-32 of A ++ B from the sums of A and of B and the length of B: a * x^(8 len_b) + b (the inversions at both ends cancel)
+uint32_t swc_crc32_combine(uint32_t a, uint32_t b, size_t len_b) {
+    uint32_t r = 1u << 31, sq = 1u << 23;   // x^0, x^8
+    for (size_t n = len_b; n != 0; n >>= 1) {
+        if (n & 1) r = crc32_mulmod(r, sq);
+        sq = crc32_mulmod(sq, sq);
+    }
+    return crc32_mulmod(r, a) ^ b;
+}
+// Adler-32 of A ++ B likewise: s1 = s1a + s1b - 1, s2 = s2a + s2b + len_b (s1a - 1), all mod 65521
+uint32_t swc_adler32_combine(uint32_t a, uint32_t b, size_t len_b) {
+    const uint64_t M = 65521u, rem = (uint64_t)len_b % M;
+    const uint64_t a1 = a & 0xFFFFu, a2 = a >> 16, b1 = b & 0xFFFFu, b2 = b >> 16;
+    const uint64_t s1 = (a1 + b1 + M - 1u) % M;
+    const uint64_t s2 = (a2 + b2 + rem * ((a1 + M - 1u) % M)) % M;
+    return (uint32_t)(s2 << 16 | s1);
+}
+
 uint32_t swc_xxh32(const uint8_t* p, size_t n, uint32_t seed) {
     const uint32_t P1 = 0x9E3779B1u, P2 = 0x85EBCA77u, P3 = 0xC2B2AE3Du, P4 = 0x27D4EB2Fu, P5 = 0x165667B1u;
     const uint8_t* e = p + n;

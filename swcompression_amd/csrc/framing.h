@@ -14,6 +14,12 @@ int gzip_parse_header(const uint8_t* d, size_t n, size_t& pos, GzipHeaderInfo* i
 int gzip_member_prepare(const uint8_t* d, size_t n, size_t pos, HostUnit& u);
 int gzip_member_finish(const uint8_t* d, size_t n, size_t data_pos, const HostUnit& u, size_t& next_pos, bool& crc_error);
 int zlib_parse_header(const uint8_t* d, size_t n, size_t& pos);
+// Deflate streams through the engine, each cut into parallel units at its flush points where it has any (framing_deflate.cpp);
+// what run_units(SWC_CODEC_DEFLATE, ...) would leave in every stream, in one launch wherever no stream has to fall back
+int run_deflate(std::vector<HostUnit>& streams);
+int run_deflate_one(HostUnit& u);
+int run_deflate_one_bounded(HostUnit& u, size_t bound);
+void set_deflate_unit_bytes(int v);   // "deflate_unit_bytes" (swc_set_tuning)
 void set_bgzf_round_members(int v);   // "bgzf_round_members" (swc_set_tuning): members per round of swc_bgzf_archive
 // many-archive batching helpers (framing_many.cpp)
 struct Lz4Plan {
@@ -35,6 +41,8 @@ size_t lzma2_announced_size(const uint8_t* p, size_t n);
 // block discovery for swc_index_blocks (framing_many.cpp)
 struct BlockRef64 { uint64_t offset, comp_len, uncomp_len; uint32_t aux; uint32_t flags = 0; };
 bool bgzf_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out);
+void deflate_unit_index(const uint8_t* in, size_t in_len, size_t unit_bytes, std::vector<BlockRef64>& out);
+size_t deflate_unit_bytes();
 bool lz4_frame_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out);
 void bzip2_magic_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out);
 void xz_block_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out);

@@ -40,6 +40,165 @@ int run_one_bounded(int codec, HostUnit& u, size_t bound) {
     return run_one(codec, u);
 }
 
+// ---- streams cut at their flush points ----------------------------------------------------------------------------------------
+// An empty stored block -- what Z_FULL_FLUSH / Z_SYNC_FLUSH, pigz and this library's own segmented encoder (kCompressSegment below)
+// put between the pieces of a stream -- ends with 00 00 FF FF on a byte boundary, and the next block starts on the next byte.  So a
+// stream is CUT behind every such marker into units that decode in parallel (include/swc_hip.h: SWC_DEFLATE_OPEN,
+// SWC_DEFLATE_JOINED), as long as no unit refers to bytes in front of itself.  The marker is only a guess -- the four bytes occur in
+// stored data and in codes too -- and the guess is checked by the decode itself: the result of the units stands only if every unit
+// in front of some unit k ended open exactly at its last byte with SWC_OK and unit k met a final block with SWC_OK; by induction
+// that is what the sequential parse does.  Anything else -- a false marker, a unit that reaches back (Z_SYNC_FLUSH), any error -- and
+// the stream is decoded whole, as ever, and THAT result is reported.
+// "deflate_unit_bytes": the least compressed size of a unit, 0 = never cut.  The default is 0 -- the host paths decode as they always
+// did -- until tools/exp_deflate_units.py has shown on the device what cutting gains; callers opt in with the knob.
+static std::atomic<size_t> g_deflate_unit_bytes{0};
+void set_deflate_unit_bytes(int v) { g_deflate_unit_bytes = (size_t)v; }
+size_t deflate_unit_bytes() { return g_deflate_unit_bytes.load(); }
+
+// The units of one raw stream (swc_index_blocks kind 3): a cut behind every marker, cuts merged until every unit but the last
+// holds at least unit_bytes, no cut at the very end.  Always at least one unit; aux = the bits of its job.
+void deflate_unit_index(const uint8_t* in, size_t len, size_t unit_bytes, std::vector<BlockRef64>& out) {
+    size_t start = 0;
+    if (unit_bytes != 0 && len >= 4) {
+        const uint8_t* p = in + 2;   // (the first 0xFF of a marker is at offset 2 or later)
+        const uint8_t* const end = in + len;
+        while (p < end) {
+            p = static_cast<const uint8_t*>(memchr(p, 0xFF, (size_t)(end - p)));
+            if (!p || p + 1 >= end) break;
+            if (p[1] == 0xFF && p[-1] == 0 && p[-2] == 0) {
+                const size_t cut = (size_t)(p - in) + 2;
+                if (cut < len && cut - start >= unit_bytes) {
+                    out.push_back({start, cut - start, 0, (uint32_t)(SWC_DEFLATE_OPEN | (out.empty() ? 0 : SWC_DEFLATE_JOINED))});
+                    start = cut;
+                }
+                p += 2;
+            } else p++;
+        }
+    }
+    out.push_back({start, len - start, 0, (uint32_t)(out.empty() ? 0 : SWC_DEFLATE_JOINED)});
+}
+
+int run_deflate(std::vector<HostUnit>& streams) {
+    const size_t ub = g_deflate_unit_bytes.load();
+    struct Run { size_t stream, first, count; };
+    std::vector<Run> runs;
+    std::vector<std::vector<BlockRef64>> refs(streams.size());
+    if (ub != 0)
+        for (size_t s = 0; s < streams.size(); s++) {
+            const HostUnit& u = streams[s];
+            if (u.in_len > ub && !u.dict && !u.chain && u.aux == 0) deflate_unit_index(u.in, u.in_len, ub, refs[s]);
+            if (refs[s].size() >= 2) runs.push_back({s, 0, refs[s].size()});
+        }
+    if (runs.empty()) return run_units(SWC_CODEC_DEFLATE, streams);
+    // one list for one launch: the streams that stay whole as they are, every other one as its run
+    std::vector<HostUnit> units;
+    std::vector<size_t> whole_at(streams.size(), (size_t)-1);
+    {
+        size_t r = 0;
+        for (size_t s = 0; s < streams.size(); s++) {
+            HostUnit& st = streams[s];
+            if (refs[s].size() < 2) { whole_at[s] = units.size(); units.push_back(std::move(st)); continue; }
+            runs[r++].first = units.size();
+            for (size_t k = 0; k < refs[s].size(); k++) {
+                HostUnit u;
+                u.in = st.in + refs[s][k].offset;
+                u.in_len = (size_t)refs[s][k].comp_len;
+                u.base = st.base ? st.base : st.in;                 // the stream is staged once, every unit a sub-range of it
+                u.base_len = st.base ? st.base_len : st.in_len;
+                u.aux = (int32_t)refs[s][k].aux;
+                u.chain = true;
+                u.sum_kind = st.sum_kind;
+                // room: six times the compressed size (the static blocks of this library's own encoder pack text 4.2 : 1; the runner's
+                // four would send every such unit round again), never more than the whole stream is said to hold; a unit that needs
+                // more says how much, and the run goes once more with exactly that
+                u.cap_hint = std::max<size_t>(65536, u.in_len * 6 + 1024);
+                if (st.cap_hint) u.cap_hint = std::min(u.cap_hint, std::max<size_t>(st.cap_hint, 64));
+                if (k == 0) { u.run_len = refs[s].size(); u.dst = st.dst; u.dst_cap = st.dst_cap; }
+                units.push_back(std::move(u));
+            }
+        }
+    }
+    int rc = run_units(SWC_CODEC_DEFLATE, units);
+    if (rc != SWC_OK) return rc;
+    // a run that lacked room: every unit has reported its exact size (phase 1 counts on past the capacity) -- once more with those
+    {
+        std::vector<HostUnit> again;
+        std::vector<size_t> which;
+        for (size_t r = 0; r < runs.size(); r++) {
+            const HostUnit& h = units[runs[r].first];
+            if (h.run_ok || units[runs[r].first + h.run_used].status != SWC_E_CAPACITY) continue;
+            which.push_back(r);
+            for (size_t k = 0; k < runs[r].count; k++) {
+                const HostUnit& o = units[runs[r].first + k];
+                HostUnit u;
+                u.in = o.in; u.in_len = o.in_len; u.base = o.base; u.base_len = o.base_len; u.aux = o.aux; u.chain = true;
+                u.sum_kind = o.sum_kind; u.run_len = o.run_len; u.dst = o.dst; u.dst_cap = o.dst_cap;
+                u.cap_hint = (size_t)std::max<uint64_t>(std::min<uint64_t>(o.need, (uint64_t)o.in_len * 1032 + 64), 64);
+                u.cap_exact = true;
+                again.push_back(std::move(u));
+            }
+        }
+        if (!again.empty()) {
+            rc = run_units(SWC_CODEC_DEFLATE, again);
+            if (rc != SWC_OK) return rc;
+            size_t at = 0;
+            for (size_t r : which)
+                for (size_t k = 0; k < runs[r].count; k++) units[runs[r].first + k] = std::move(again[at++]);
+        }
+    }
+    for (size_t s = 0; s < streams.size(); s++) if (whole_at[s] != (size_t)-1) streams[s] = std::move(units[whole_at[s]]);
+    std::vector<size_t> fallback;
+    for (const Run& r : runs) {
+        HostUnit& st = streams[r.stream];
+        HostUnit& h = units[r.first];
+        if (!h.run_ok) { fallback.push_back(r.stream); continue; }
+        const HostUnit& last = units[r.first + h.run_used];
+        st.status = SWC_OK;
+        st.in_consumed = (size_t)(last.in - st.in) + last.in_consumed;
+        st.out = std::move(h.out);
+        st.in_dst = h.in_dst;
+        st.out_size = h.run_bytes;
+        st.aux_out = 0;
+        if (st.sum_kind == SWC_SUM_CRC32 || st.sum_kind == SWC_SUM_ADLER32) {   // the units' sums, combined: no pass over the joined output
+            bool valid = true;
+            uint32_t sum = st.sum_kind == SWC_SUM_CRC32 ? 0u : 1u;
+            for (size_t k = 0; k <= h.run_used && valid; k++) {
+                const HostUnit& u = units[r.first + k];
+                valid = u.sum_valid;
+                sum = st.sum_kind == SWC_SUM_CRC32 ? swc_crc32_combine(sum, (uint32_t)u.sum, u.out_size) : swc_adler32_combine(sum, (uint32_t)u.sum, u.out_size);
+            }
+            st.sum = sum;
+            st.sum_valid = valid;
+        }
+    }
+    if (!fallback.empty()) {   // as ever, and that result is the stream's
+        std::vector<HostUnit> whole(fallback.size());
+        for (size_t i = 0; i < fallback.size(); i++) whole[i] = std::move(streams[fallback[i]]);
+        stat_add(3, (long long)fallback.size());
+        rc = run_units(SWC_CODEC_DEFLATE, whole);
+        for (size_t i = 0; i < fallback.size(); i++) streams[fallback[i]] = std::move(whole[i]);
+        if (rc != SWC_OK) return rc;
+    }
+    return SWC_OK;
+}
+int run_deflate_one(HostUnit& u) {
+    std::vector<HostUnit> v(1);
+    v[0] = std::move(u);
+    int st = run_deflate(v);
+    u = std::move(v[0]);
+    return st;
+}
+// run_one_bounded for a Deflate stream
+int run_deflate_one_bounded(HostUnit& u, size_t bound) {
+    if (u.in_len <= bound) return run_deflate_one(u);
+    HostUnit t = u;
+    t.in_len = bound;
+    int st = run_deflate_one(t);
+    if (st != SWC_OK) return st;
+    if (t.status == SWC_OK && t.in_consumed + 64 <= bound) { u = std::move(t); return SWC_OK; }
+    return run_deflate_one(u);
+}
+
 void give(const std::vector<uint8_t>& src, uint8_t** out, size_t* out_len) {
     uint8_t* p = host_result(src.size());
     if (!p) throw std::bad_alloc();   // (host_result is malloc: the entry points' function-try-blocks turn this into SWC_E_DEVICE)
@@ -184,7 +343,7 @@ int swc_deflate_decompress(const uint8_t* in, size_t in_len, uint8_t** out, size
     if (!out || !out_len || (in_len && !in)) return SWC_E_INVALID_ARGUMENT;
     HostUnit u;
     u.in = in; u.in_len = in_len;
-    int st = run_one(SWC_CODEC_DEFLATE, u);
+    int st = run_deflate_one(u);
     if (st) { give_empty(out, out_len); return st; }
     if (in_consumed) *in_consumed = u.in_consumed;
     if (u.status) { give_empty(out, out_len); return u.status; }       // DeflateError cases carry no data
@@ -202,7 +361,7 @@ int swc_gzip_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, size_t* 
     if (st) { give_empty(out, out_len); return st; }
     const size_t data_pos = (size_t)(u.in - in);
     u.sum_kind = 1;                                                    // CRC-32 on the device, behind the decode
-    st = run_one(SWC_CODEC_DEFLATE, u);
+    st = run_deflate_one(u);
     if (st) { give_empty(out, out_len); return st; }
     size_t next; bool crc_error;
     st = gzip_member_finish(in, in_len, data_pos, u, next, crc_error);
@@ -313,7 +472,7 @@ int swc_gzip_multi_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, si
         if (st) break;
         u.cap_hint = 0;                                                // ISIZE guess only valid for the last member
         const size_t data_pos = (size_t)(u.in - in);
-        st = run_one_bounded(SWC_CODEC_DEFLATE, u, walk_bound);
+        st = run_deflate_one_bounded(u, walk_bound);
         if (st) break;
         walk_bound = std::max<size_t>(walk_bound, 4 * u.in_consumed + 65536);   // the next member is probably of this size
         bool crc_error;
@@ -603,7 +762,7 @@ int swc_zlib_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, size_t* 
     HostUnit u;
     u.in = in + p; u.in_len = in_len - p;
     u.sum_kind = 2;                                                    // Adler-32 on the device, behind the decode
-    st = run_one(SWC_CODEC_DEFLATE, u);
+    st = run_deflate_one(u);
     if (st) { give_empty(out, out_len); return st; }
     if (u.status) { give_empty(out, out_len); return u.status; }
     size_t q = p + u.in_consumed;

@@ -63,7 +63,7 @@ int many_single_unit(int kind, const uint8_t* const* archives, const size_t* len
         data_pos.push_back(p);
     }
     if (!units.empty()) {
-        int st = run_units(codec, units);
+        int st = codec == SWC_CODEC_DEFLATE ? run_deflate(units) : run_units(codec, units);   // (flushed streams as runs of units, in the same launch)
         if (st) return st;
     }
     for (size_t k = 0; k < units.size(); k++) {
@@ -468,6 +468,7 @@ int swc_index_blocks(int kind, const uint8_t* in, size_t len, swc_block_ref* ref
     int st = SWC_OK;
     switch (kind) {
         case 1: ok = bgzf_index(in, len, v); break;
+        case 3: deflate_unit_index(in, len, deflate_unit_bytes(), v); break;
         case 4: ok = lz4_frame_index(in, len, v); break;
         case 5: bzip2_magic_index(in, len, v); break;
         case 6: xz_block_index(in, len, v); break;

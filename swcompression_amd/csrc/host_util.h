@@ -77,6 +77,9 @@ struct HostUnit {
     // runner lays the outputs of a chain out back to back and never launches one of its units again on its own: a status that
     // would otherwise mean "once more with more room" (SWC_E_CAPACITY, SWC_E_NEED_WORKSPACE) is the caller's to act on.
     bool chain = false;
+    // Deflate: the unit is part of a RUN -- the units one stream was cut into at its flush points (framing_deflate.cpp), `chain` set on
+    // all of them, SWC_DEFLATE_JOINED on all but the head.  run_len: on the head, the number of units of the run (0 on the others).
+    size_t run_len = 0;
     uint64_t extra = 0;          // codec specific (goes to Job::dict_len when dict == nullptr)
     uint64_t dict_value = 0;     // codec specific integer carried in Job::dict when dict == nullptr (LZMA: dictionary size)
     // Optional: where the output is wanted (a place inside the caller's final buffer, `dst_cap` bytes of room).  If the
@@ -96,7 +99,12 @@ struct HostUnit {
     size_t size() const { return in_dst ? out_size : out.size(); }
     size_t in_consumed = 0;
     int32_t status = SWC_OK;
-    int32_t aux_out = 0;         // codec specific result (bzip2: computed block CRC)
+    int32_t aux_out = 0;         // codec specific result (bzip2: computed block CRC; Deflate: SWC_DEFLATE_OPEN where the unit ended open)
+    // results of a Deflate run, on its head: the units in front of unit run_used ended open at their last byte; run_ok: unit run_used
+    // met a final block, and the head's output is the stream's -- run_bytes of it (out_size stays the head's own share)
+    bool run_ok = false;
+    size_t run_used = 0, run_bytes = 0;
+    uint64_t need = 0;           // Deflate run units: out_len as the job reported it (the room it needs, for SWC_E_CAPACITY)
 };
 
 // Stage units to HBM, run ONE batched launch of `codec` (re-launching only the units that reported
@@ -117,7 +125,7 @@ struct Trace {
 };
 
 // swc_stat counters (api.cpp)
-void stat_add(int which, long long v);   // 0 launches, 1 units, 2 xz_cache_hits
+void stat_add(int which, long long v);   // 0 launches, 1 units, 2 xz_cache_hits, 3 deflate_unit_fallbacks
 
 }  // namespace swc
 #endif

@@ -1496,6 +1496,9 @@ SWC_D void inflate_sync_job(Job& job, SyncLds* sl, uint8_t* ws, size_t ws_bytes,
         sp.sub = (SWC_AS_GLOBAL uint32_t*)(s0 + kSpillSub);
     }
     int st = SWC_OK;
+    // SWC_DEFLATE_OPEN (include/swc_hip.h): the unit of a stream cut at its flush points may end where a block header would start
+    const bool open = (job.aux & kDeflateOpen) != 0;
+    bool ended_open = false;
     if (lo == 0 || ln.prov == nullptr) {
         st = SWC_E_NEED_WORKSPACE;   // (an area smaller than swc_batch_workspace_bytes asks for)
         ln.br.init((gcptr)job.in, 0, 0);
@@ -1507,6 +1510,7 @@ SWC_D void inflate_sync_job(Job& job, SyncLds* sl, uint8_t* ws, size_t ws_bytes,
         if ((uint64_t)ln.br.len * 8 < 10) st = SWC_E_DEFLATE_WRONG_BLOCK_TYPE;  // :36
         while (st == SWC_OK) {
             ln.br.refill();
+            if (open && ln.br.bc == 0) { ended_open = true; break; }   // exactly at bit 8 * in_len: the unit ends here, the stream goes on
             if (ln.br.bc < 3) { st = SWC_E_REF_TRAP; break; }   // a second or later block header past the end: LsbBitReader.bit() traps
             const uint32_t is_last = ln.br.bits(1);
             const uint32_t type = ln.br.bits(2);
@@ -1565,6 +1569,7 @@ SWC_D void inflate_sync_job(Job& job, SyncLds* sl, uint8_t* ws, size_t ws_bytes,
     job.in_consumed = consumed > job.in_len ? job.in_len : consumed;
     job.out_len = ln.pos;
     job.status = st;
+    if (!ended_open) job.aux &= ~kDeflateOpen;   // (OUT: the bit stays only where the unit ended open)
 }
 
 }  // namespace inflate

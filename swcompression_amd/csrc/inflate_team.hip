@@ -40,7 +40,7 @@ __global__ __launch_bounds__(64 * inflate::kTeamWaves) void swc_inflate_team_ker
         if (threadIdx.x == 0) team_shared.cmd = 0u;
         Job job = jobs[g];
         inflate::inflate_sync_job<true>(job, &team_lds[0], wm.area(g), wm.bytes(g), (int)threadIdx.x, kWave, nullptr, &tm);
-        if (threadIdx.x == 0) put_result(jobs, g, job);
+        if (threadIdx.x == 0) put_result<true>(jobs, g, job);   // (aux: SWC_DEFLATE_OPEN is an OUT bit)
     } else {
         inflate::team_helper_loop(tm, (int)threadIdx.y);
     }

@@ -22,6 +22,7 @@
 #include "inflate_sync.h"
 #include "lz_resolve.h"
 #include "lz_copy.h"
+#include "deflate_place.h"
 #include "lz4_lane.h"
 #include "lz4_wave.h"
 #include "lz4_chain.h"
@@ -167,7 +168,16 @@ __global__ __launch_bounds__(64, SWC_SYNC_WAVES_PER_SIMD) void swc_inflate_sync_
     if (g >= n) return;
     Job job = jobs[g];
     inflate::inflate_sync_job(job, &sync_lds, wm.area(g), wm.bytes(g), (int)threadIdx.x, kWave, prof ? prof + 32 * (size_t)g : nullptr);
-    if (threadIdx.x == 0) put_result(jobs, g, job);
+    if (threadIdx.x == 0) put_result<true>(jobs, g, job);   // (aux: SWC_DEFLATE_OPEN is an OUT bit)
+}
+
+// Between the phases: the joined units of the launch get their place (deflate_place.h), one wavefront per tile of 64 consecutive
+// jobs; a tile without a joined job ends after one ballot.
+__global__ __launch_bounds__(64) void swc_deflate_place_kernel(Job* jobs, uint32_t n) {
+    defp::place_tile(jobs, n, blockIdx.x);
+}
+static void launch_deflate_place(Job* jobs, size_t n, hipStream_t stream) {
+    hipLaunchKernelGGL(swc_deflate_place_kernel, dim3((unsigned)((n + defp::kTile - 1) / defp::kTile)), dim3(kWave), 0, stream, jobs, (uint32_t)n);
 }
 
 // Phase 2: one stream per workgroup of 512 threads, 64 KiB LDS ring (32 KiB of history + span + cells) -> 2 workgroups per CU.
@@ -303,6 +313,7 @@ constexpr size_t kTeamMaxStreams = 256, kTeamForceStreams = 4096;
 static hipError_t crc32_consts_ready(hipStream_t stream);
 static void launch_crc32_group(const Job* jobs, size_t n, uint32_t* crcs, hipStream_t stream);
 static void launch_inflate_phase2(Job* jobs, size_t n, const WsMap& wm, const uint32_t* order, uint32_t* crcs, hipStream_t stream) {
+    launch_deflate_place(jobs, n, stream);   // (phase 1 has run on every path that comes here: the sizes are in the job list)
     if (wave_copier(n)) {
         if (crcs) {
             hipLaunchKernelGGL(swc_lz_copy_crc32_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, jobs, (uint32_t)n, wm, order, crcs);
