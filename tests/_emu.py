@@ -1,5 +1,6 @@
-"""ctypes binding of tests/host_emu/libswc_emu.so -- the device decoders compiled for the host.
-TEST INFRASTRUCTURE ONLY (see tests/host_emu/emu.cpp)."""
+"""ctypes binding of tests/host_emu/libswc_emu.so -- the device code compiled for the host: the one library of the CPU tier, its one
+build recipe and its one rule for rebuilding.  The _emu_*.py modules are layers over `lib`.  TEST INFRASTRUCTURE ONLY (see
+tests/host_emu/emu.cpp)."""
 import ctypes as C
 import os
 import subprocess
@@ -16,14 +17,27 @@ class Job(C.Structure):
                 ("dict", C.c_void_p), ("dict_len", C.c_uint64)]
 
 
+def _compile(out, src, opt, how):
+    subprocess.run(["g++"] + list(opt) + ["-std=c++17", "-DSWC_HOST_EMULATION"] + list(how) +
+                   ["-Wno-unknown-pragmas", "-pthread", "-o", out, os.path.join(_DIR, src)], check=True)
+
+
 def compile_lib(out, opt=("-O2", "-g")):
-    """The one recipe of the emulation library; the ASAN tests pass their own optimisation and sanitizer flags."""
-    subprocess.run(["g++"] + list(opt) + ["-std=c++17", "-DSWC_HOST_EMULATION", "-fPIC", "-shared",
-                    "-Wno-unknown-pragmas", "-pthread", "-o", out, os.path.join(_DIR, "emu.cpp")], check=True)
+    """The one recipe of the emulation library (emu.cpp includes the other sources); the ASAN tests pass their own optimisation and
+    sanitizer flags."""
+    _compile(out, "emu.cpp", opt, ("-fPIC", "-shared"))
+
+
+def compile_program(out, src, define, opt=("-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")):
+    """A source of host_emu that has a main of its own behind -D`define`, as a stand-alone program: by default with the address and
+    undefined-behaviour sanitizers.  Run as a program, never loaded into python."""
+    _compile(out, src, opt, ("-D" + define,))
 
 
 def build(force=False):
-    srcs = [os.path.join(_DIR, "emu.cpp")] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
+    """Rebuilds the library when any source of host_emu or any header of csrc is newer than it."""
+    srcs = [os.path.join(_DIR, f) for f in os.listdir(_DIR) if f.endswith((".cpp", ".h"))]
+    srcs += [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
     if not force and os.path.exists(_LIB) and all(os.path.getmtime(_LIB) >= os.path.getmtime(s) for s in srcs):
         return
     compile_lib(_LIB)
@@ -38,21 +52,46 @@ def set_order(order):
     lib.emu_set_order(C.c_int(order))
 
 
+class Guarded:
+    """`n` bytes that start `residue` bytes past an `align`-byte boundary, with at least `guard` bytes of `fill` on both sides:
+    .addr is their address."""
+
+    def __init__(self, n, residue=0, align=16, guard=16, fill=0xA5, data=b""):
+        self._buf = C.create_string_buffer(align + guard + residue + n + guard)
+        C.memset(self._buf, fill, len(self._buf))
+        base = C.addressof(self._buf)
+        self.addr = base + (-base) % align + guard + residue
+        self.n = n
+        self._fill = bytes([fill])
+        C.memmove(self.addr, bytes(data), len(data))
+
+    def read(self, lo=0, hi=None):
+        return C.string_at(self.addr + lo, (self.n if hi is None else hi) - lo)
+
+    def check(self, what="", used=None):
+        """Asserts that every byte in front of the n bytes and every byte behind them -- behind the first `used` of them, where given --
+        still holds the fill value."""
+        base = C.addressof(self._buf)
+        front, end = self.addr - base, self.addr + (self.n if used is None else used)
+        back = base + len(self._buf) - end
+        assert C.string_at(base, front) == self._fill * front, "guard bytes in front overwritten (%s)" % what
+        assert C.string_at(end, back) == self._fill * back, "guard bytes behind overwritten (%s)" % what
+
+
 def run_batch(fn_name, inputs, caps, aux=None, dicts=None, extra=None, fn_args=(), dict_ptr_values=None, misalign=0, lib=None):
     """inputs: list[bytes]; caps: list[int].  Returns list of (status, out_bytes, in_consumed, out_len).
-    misalign: the output buffers start that many bytes past a 16-byte boundary.  lib: another build of the library (ASAN)."""
+    misalign: the output buffers start that many bytes past a 16-byte boundary, 16 guard bytes on either side.  lib: another build
+    of the library (ASAN)."""
     n = len(inputs)
     jobs = (Job * n)()
-    keep = []
+    keep, outs = [], []
     for i, (data, cap) in enumerate(zip(inputs, caps)):
         ib = C.create_string_buffer(bytes(data), max(len(data), 1))
-        ob = C.create_string_buffer(max(cap, 1) + 16 + 48)  # 16 guard bytes on either side + alignment slack
-        o0 = (-C.addressof(ob)) % 16 + 16 + misalign
-        C.memset(C.addressof(ob), 0xA5, len(ob))
-        keep.append((ib, ob, o0))
+        keep.append(ib)
+        outs.append(Guarded(cap, misalign))
         jobs[i].in_ = C.addressof(ib)
         jobs[i].in_len = len(data)
-        jobs[i].out = C.addressof(ob) + o0
+        jobs[i].out = outs[i].addr
         jobs[i].out_cap = cap
         jobs[i].aux = 0 if aux is None else aux[i]
         if dicts is not None and dicts[i] is not None:
@@ -67,12 +106,8 @@ def run_batch(fn_name, inputs, caps, aux=None, dicts=None, extra=None, fn_args=(
     getattr(lib or globals()["lib"], fn_name)(jobs, C.c_size_t(n), *fn_args)
     res = []
     for i in range(n):
-        ib, ob, o0 = keep[i] if dicts is None else [k for k in keep if isinstance(k, tuple)][i]
-        cap = caps[i]
-        raw = ob.raw
-        assert raw[o0 + cap:o0 + cap + 16] == b"\xA5" * 16 and raw[:o0] == b"\xA5" * o0, "guard bytes overwritten (job %d)" % i
-        nout = min(jobs[i].out_len, cap)
-        res.append((jobs[i].status, raw[o0:o0 + nout], jobs[i].in_consumed, jobs[i].out_len))
+        outs[i].check("job %d" % i)
+        res.append((jobs[i].status, outs[i].read(0, min(jobs[i].out_len, caps[i])), jobs[i].in_consumed, jobs[i].out_len))
     return res
 
 
@@ -125,11 +160,10 @@ lib.emu_checksum.restype = C.c_uint64
 def checksum(kind, data, misalign=0):
     """kind: 1 crc32, 2 adler32, 3 crc64, 4 bzip2crc32, 5 xxh32 (swc_checksum of include/swc_hip.h).  The data are
     placed `misalign` bytes past a 64-byte boundary."""
-    data = bytes(data)
-    buf = C.create_string_buffer(len(data) + 128)
-    base = (C.addressof(buf) + 63) // 64 * 64 + misalign
-    C.memmove(base, data, len(data))
-    return lib.emu_checksum(kind, base, len(data))
+    buf = Guarded(len(data), misalign, align=64, data=data)
+    got = lib.emu_checksum(kind, buf.addr, buf.n)
+    buf.check("checksum %d" % kind)
+    return got
 
 
 lib.emu_crc32_wave.argtypes = [C.c_void_p, C.c_size_t]
@@ -138,11 +172,10 @@ lib.emu_crc32_wave.restype = C.c_uint32
 
 def crc32_wave(data, misalign=0):
     """CRC-32 by the wave-per-stream code of the device (crc32_wave.h), the data `misalign` bytes past a 64-byte boundary."""
-    data = bytes(data)
-    buf = C.create_string_buffer(len(data) + 128)
-    base = (C.addressof(buf) + 63) // 64 * 64 + misalign
-    C.memmove(base, data, len(data))
-    return lib.emu_crc32_wave(base, len(data))
+    buf = Guarded(len(data), misalign, align=64, data=data)
+    got = lib.emu_crc32_wave(buf.addr, buf.n)
+    buf.check("crc32_wave")
+    return got
 
 
 lib.emu_delta.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t, C.c_uint]

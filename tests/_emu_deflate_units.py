@@ -1,49 +1,21 @@
-"""ctypes binding of tests/host_emu/libswc_emu_deflate_units.so -- a Deflate launch with joined and open units (csrc/inflate_sync.h,
-deflate_place.h, lz_copy.h, lz_resolve.h) compiled for the host.  TEST INFRASTRUCTURE ONLY (see
-tests/host_emu/emu_deflate_units.cpp).  The recipe is that of _emu.compile_lib."""
+"""A Deflate launch with joined and open units (csrc/inflate_sync.h, deflate_place.h, lz_copy.h, lz_resolve.h) on the host emulation:
+a thin layer over _emu (tests/host_emu/emu_deflate_units.cpp).  TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
-import os
 import struct
-import subprocess
 
+import _emu
 from _emu import Job
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_DIR = os.path.join(_HERE, "host_emu")
-_SRC = os.path.join(_DIR, "emu_deflate_units.cpp")
-_LIB = os.path.join(_DIR, "libswc_emu_deflate_units.so")
-_CSRC = os.path.join(os.path.dirname(_HERE), "swcompression_amd", "csrc")
+lib = _emu.lib
+set_order = _emu.set_order
 
 GUARD = 16
 JOINED, OPEN = 1, 2
 
 
-def compile_lib(out, opt=("-O2", "-g")):
-    subprocess.run(["g++"] + list(opt) + ["-std=c++17", "-DSWC_HOST_EMULATION", "-fPIC", "-shared",
-                    "-Wno-unknown-pragmas", "-pthread", "-o", out, _SRC], check=True)
-
-
-def compile_program(out, opt=("-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")):
-    """The stand-alone program of emu_deflate_units.cpp (its own main), by default with the address and undefined-behaviour sanitizers."""
-    subprocess.run(["g++"] + list(opt) + ["-std=c++17", "-DSWC_HOST_EMULATION", "-DEMU_DEFLATE_UNITS_MAIN",
-                    "-Wno-unknown-pragmas", "-pthread", "-o", out, _SRC], check=True)
-
-
-def build(force=False):
-    srcs = [_SRC] + [os.path.join(_CSRC, f) for f in ("deflate_place.h", "inflate_sync.h", "inflate_lane.h", "lz_copy.h", "lz_resolve.h",
-                                                       "simt.h", "swc_common.h")]
-    if not force and os.path.exists(_LIB) and all(os.path.getmtime(_LIB) >= os.path.getmtime(s) for s in srcs):
-        return
-    compile_lib(_LIB)
-
-
-build()
-lib = C.CDLL(_LIB)
-
-
-def set_order(order):
-    """Thread order of the emulated SIMT regions (csrc/simt.h): 0 forward, 1 reverse, 2 shuffled."""
-    lib.emu_set_order(C.c_int(order))
+def compile_program(out):
+    """The stand-alone program of emu_deflate_units.cpp (its own main), with the address and undefined-behaviour sanitizers."""
+    _emu.compile_program(out, "emu_deflate_units.cpp", "EMU_DEFLATE_UNITS_MAIN")
 
 
 def place(sizes, caps, aux, base=0x10000, reversed_=False):
@@ -82,28 +54,23 @@ def run_units(units, misalign=0, copier=1, team=0, reversed_=False, head_gap=Non
                 if not v["aux"] & JOINED:
                     break
                 room += v["cap"]
-            buf = C.create_string_buffer(GUARD + 32 + room + GUARD)
-            C.memset(buf, 0xA5, len(buf))
-            o0 = (-C.addressof(buf)) % 16 + GUARD + misalign
-            bufs[i] = (buf, o0, room)
+            bufs[i] = _emu.Guarded(room, misalign, guard=GUARD)
             if not (u["aux"] & JOINED):
-                jobs[i].out = C.addressof(buf) + o0
+                jobs[i].out = bufs[i].addr
         head_of.append(max(k for k in bufs if k <= i))
     lib.emu_deflate_units(jobs, C.c_size_t(n), C.c_int(copier), C.c_int(team), C.c_int(1 if reversed_ else 0))
     res = []
     used = {h: 0 for h in bufs}
     for i in range(n):
-        buf, o0, room = bufs[head_of[i]]
-        rel = (jobs[i].out or 0) - (C.addressof(buf) + o0)
+        buf = bufs[head_of[i]]
+        rel = (jobs[i].out or 0) - buf.addr
         k = min(jobs[i].out_len, jobs[i].out_cap)
-        ok = jobs[i].out is not None and 0 <= rel and rel + k <= room
+        ok = jobs[i].out is not None and 0 <= rel and rel + k <= buf.n
         if ok:
             used[head_of[i]] = max(used[head_of[i]], rel + k)
-        res.append((jobs[i].status, jobs[i].out_len, jobs[i].in_consumed, jobs[i].aux, rel if ok else None, buf.raw[o0 + rel:o0 + rel + k] if ok else None))
-    for h, (buf, o0, room) in bufs.items():
-        raw = buf.raw
-        assert raw[:o0] == b"\xA5" * o0, "bytes in front of the run of job %d overwritten" % h
-        assert raw[o0 + used[h]:] == b"\xA5" * (len(raw) - o0 - used[h]), "bytes behind the run of job %d overwritten" % h
+        res.append((jobs[i].status, jobs[i].out_len, jobs[i].in_consumed, jobs[i].aux, rel if ok else None, buf.read(rel, rel + k) if ok else None))
+    for h, buf in bufs.items():
+        buf.check("the run of job %d" % h, used=used[h])
     return res
 
 

@@ -2,11 +2,11 @@
 // (g++ -DSWC_HOST_EMULATION): the uniform parts run once, the threads of every SIMT region (csrc/simt.h) one
 // after another in a selectable order.  Lets the CPU-only test tier exercise
 // the exact source the gfx950 kernels are compiled from against the oracle.  Never shipped, never
-// linked into libswc_hip.so.
-#include <vector>
-#include <cstring>
+// linked into libswc_hip.so.  This file is the whole library: the drivers of the later features (emu_bgzf.cpp, emu_crc_tail.cpp,
+// emu_lz4_linked.cpp, emu_deflate_units.cpp) are included at its end, so that one compile shares the template instantiations.
 #include <algorithm>
 #include <memory>
+#include "emu_util.h"
 #include "../../swcompression_amd/csrc/inflate_lane.h"
 #include "../../swcompression_amd/csrc/inflate_sync.h"
 #include "../../swcompression_amd/csrc/lz4_lane.h"
@@ -21,9 +21,8 @@
 #include "../../swcompression_amd/csrc/bzip2_comp.h"
 #include "../../swcompression_amd/csrc/crc32_group.h"
 
-extern "C" void emu_set_order(int o) { swc::simt::g_order = o; }
-// phase 2: 1 = the record-granular copier of lz_copy.h as the library ships it (Deflate: 5 KiB window, LZ4: 8 KiB), 3 = the 5 KiB
-// window for both, 2 = the 8 KiB window for both, 0 = the byte-cell resolver of lz_resolve.h
+// phase 2: 1 = the record-granular copier of lz_copy.h as the library ships it (Deflate: 6 KiB window, LZ4: 7 KiB), 3 = the 6 KiB
+// window for both, 2 = the 7 KiB window for both, 0 = the byte-cell resolver of lz_resolve.h
 static int g_copier = 1;
 extern "C" void emu_set_copier(int on) { g_copier = on; }
 // (the two window configurations the library ships: kernels.hip)
@@ -60,22 +59,14 @@ extern "C" void emu_set_deflate_team(int on) { g_team = on; }
 extern "C" uint64_t emu_team_adopted(int reset) { const uint64_t v = swc::inflate::g_team_adopted; if (reset) swc::inflate::g_team_adopted = 0; return v; }
 extern "C" void emu_inflate_sync(swc::Job* jobs, size_t n) {
     alignas(16) static swc::inflate::SyncLds sl;
-    alignas(16) static swc::inflate::SyncLds tl[swc::inflate::kTeamWaves];
-    alignas(16) static swc::inflate::TeamShared tsh;
     alignas(16) static swc::lzr::Lds<512, 16> rl;
     for (size_t g = 0; g < n; g++) {
         std::memset(&sl, 0xEE, sizeof sl);
         size_t wsb = swc::lzr::ws_bytes_per_job(jobs[g].out_cap);
         std::vector<uint8_t> ws(wsb + 16, (uint8_t)0xCD);
         if (g_team) {
-            std::memset(tl, 0xEE, sizeof tl);
-            std::memset(&tsh, 0xEE, sizeof tsh);
-            for (auto& h : tsh.hgen) h = 0;
-            tsh.cmd = 0;
-            std::vector<uint8_t> rows((swc::inflate::kTeamWaves - 1) * swc::inflate::kTeamProvBytes + 16, (uint8_t)0xCD);
-            swc::inflate::Team tm;
-            tm.sh = &tsh; tm.lds = tl; tm.scratch = rows.data(); tm.helpers = swc::inflate::kTeamWaves - 1; tm.gen = 0;
-            swc::inflate::inflate_sync_job<true>(jobs[g], &tl[0], ws.data(), wsb, 0, 1, nullptr, &tm);
+            EmuTeam t;
+            swc::inflate::inflate_sync_job<true>(jobs[g], t.tm.lds, ws.data(), wsb, 0, 1, nullptr, &t.tm);
         } else
         swc::inflate::inflate_sync_job(jobs[g], &sl, ws.data(), wsb, 0, 1);
         if (g_copier) {
@@ -372,13 +363,7 @@ uint64_t run_group(F body) {
 }  // namespace
 
 // the wave-per-stream CRC-32 (crc32_wave.h): constants built once, the 64 lanes run one after the other
-#include "../../swcompression_amd/csrc/crc32_wave.h"
-extern "C" uint32_t emu_crc32_wave(const uint8_t* p, size_t n) {
-    static swc::crcw::WaveConsts consts;
-    static bool built = false;
-    if (!built) { swc::crcw::build_consts<1>(&consts, 0); built = true; }
-    return swc::crcw::crc32_wave(p, n, &consts);
-}
+extern "C" uint32_t emu_crc32_wave(const uint8_t* p, size_t n) { return swc::crcw::crc32_wave(p, n, emu_wave_consts()); }
 
 // kind as swc_checksum (include/swc_hip.h); T = 64 emulated threads per group
 extern "C" uint64_t emu_checksum(int kind, const uint8_t* p, size_t n) {
@@ -470,3 +455,9 @@ extern "C" int emu_bzip2_compress(const uint8_t* data, size_t len, int level, ui
     free(res);
     return st;
 }
+
+// ---- the drivers that have a source of their own (two of them double as stand-alone sanitizer programs) ----------------------
+#include "emu_bgzf.cpp"
+#include "emu_crc_tail.cpp"
+#include "emu_lz4_linked.cpp"
+#include "emu_deflate_units.cpp"

@@ -1,22 +1,12 @@
 // emu_bgzf.cpp -- TEST INFRASTRUCTURE.  The BGZF writer's device code (swcompression_amd/csrc/bgzf_pack.h) and the wave CRC it
 // uses, built for the HOST (g++ -DSWC_HOST_EMULATION): the 64 threads of every SIMT region run one after another in the order
-// emu_set_order selects.  A translation unit of its own (tests/_emu_bgzf.py); never shipped.
-#include <vector>
-#include <cstring>
+// emu_set_order selects.  Part of libswc_emu.so (emu.cpp includes it; tests/_emu_bgzf.py); the writer's CRC launch is
+// emu_crc32_wave.  Never shipped.
+#include "emu_util.h"
 #include "../../swcompression_amd/csrc/bgzf_pack.h"
-#include "../../swcompression_amd/csrc/crc32_wave.h"
 
 using swc::Job;
 namespace bg = swc::bgzf;
-
-extern "C" void emu_set_order(int o) { swc::simt::g_order = o; }
-
-extern "C" uint32_t emu_bgzf_crc32(const uint8_t* p, size_t n) {
-    static swc::crcw::WaveConsts consts;
-    static bool built = false;
-    if (!built) { swc::crcw::build_consts<1>(&consts, 0); built = true; }
-    return swc::crcw::crc32_wave(p, n, &consts);
-}
 
 // the workspace plan as the library cuts it: out[0..9) = n, stride, cjobs, kjobs, crcs, offs, res, slots, bytes
 extern "C" void emu_bgzf_plan(uint64_t len, uint64_t bs, uint64_t* out) {

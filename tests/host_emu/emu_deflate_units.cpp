@@ -1,21 +1,17 @@
 // emu_deflate_units.cpp -- TEST INFRASTRUCTURE.  A Deflate launch with joined and open units -- phase 1 with the OPEN rule
 // (csrc/inflate_sync.h), the placing scan (csrc/deflate_place.h), the copy (csrc/lz_copy.h or csrc/lz_resolve.h) -- compiled for
-// the HOST (g++ -DSWC_HOST_EMULATION): the three steps one after the other over all jobs, as kernels.hip issues them.  Never shipped.
+// the HOST (g++ -DSWC_HOST_EMULATION): the three steps one after the other over all jobs, as kernels.hip issues them.  Part of
+// libswc_emu.so (emu.cpp includes it).  Never shipped.
 //
 // With -DEMU_DEFLATE_UNITS_MAIN the file is a stand-alone program (for -fsanitize=address,undefined): it reads runs and what is
 // expected of them from a file written by tests/test_deflate_units_emulation.py, runs every case at the sixteen alignments of its
 // buffers, in the three lane orders, with both copiers, both copy orders and the team instantiation of phase 1, and compares; the
 // placing scan runs on the size lists of the same test as well.
-#include <vector>
-#include <cstring>
-#include <cstdio>
-#include <cstdlib>
+#include "emu_util.h"
 #include "../../swcompression_amd/csrc/inflate_lane.h"
 #include "../../swcompression_amd/csrc/inflate_sync.h"
 #include "../../swcompression_amd/csrc/lz_copy.h"
 #include "../../swcompression_amd/csrc/deflate_place.h"
-
-extern "C" void emu_set_order(int o) { swc::simt::g_order = o; }
 
 // The placing scan alone over a job list whose out_len / out_cap / aux are given: tiles in forward (0) or reverse (1) order.
 extern "C" void emu_deflate_place(swc::Job* jobs, size_t n, int tiles_reversed) {
@@ -28,8 +24,6 @@ extern "C" void emu_deflate_place(swc::Job* jobs, size_t n, int tiles_reversed) 
 extern "C" void emu_deflate_units(swc::Job* jobs, size_t n, int copier, int team, int reversed) {
     using namespace swc;
     alignas(16) static inflate::SyncLds sl;
-    alignas(16) static inflate::SyncLds tl[inflate::kTeamWaves];
-    alignas(16) static inflate::TeamShared tsh;
     alignas(16) static lzr::Lds<512, 16> rl;
     alignas(16) static lzc::Lds<lzc::CfgDeflate::kWin> cl;
     std::vector<std::vector<uint8_t>> ws(n);
@@ -38,14 +32,8 @@ extern "C" void emu_deflate_units(swc::Job* jobs, size_t n, int copier, int team
         ws[g].assign(wsb + 16, (uint8_t)0xCD);
         Job job = jobs[g];
         if (team) {
-            std::memset(tl, 0xEE, sizeof tl);
-            std::memset(&tsh, 0xEE, sizeof tsh);
-            for (auto& h : tsh.hgen) h = 0;
-            tsh.cmd = 0;
-            std::vector<uint8_t> rows((inflate::kTeamWaves - 1) * inflate::kTeamProvBytes + 16, (uint8_t)0xCD);
-            inflate::Team tm;
-            tm.sh = &tsh; tm.lds = tl; tm.scratch = rows.data(); tm.helpers = inflate::kTeamWaves - 1; tm.gen = 0;
-            inflate::inflate_sync_job<true>(job, &tl[0], ws[g].data(), wsb, 0, 1, nullptr, &tm);
+            EmuTeam t;
+            inflate::inflate_sync_job<true>(job, t.tm.lds, ws[g].data(), wsb, 0, 1, nullptr, &t.tm);
         } else {
             std::memset(&sl, 0xEE, sizeof sl);
             inflate::inflate_sync_job(job, &sl, ws[g].data(), wsb, 0, 1);
@@ -69,12 +57,6 @@ extern "C" void emu_deflate_units(swc::Job* jobs, size_t n, int copier, int team
 
 #ifdef EMU_DEFLATE_UNITS_MAIN
 namespace {
-struct Reader {
-    std::vector<uint8_t> d;
-    size_t at = 0;
-    uint32_t u32() { uint32_t v; if (at + 4 > d.size()) { fprintf(stderr, "case file too short\n"); exit(2); } memcpy(&v, d.data() + at, 4); at += 4; return v; }
-    std::vector<uint8_t> bytes(size_t n) { if (at + n > d.size()) { fprintf(stderr, "case file too short\n"); exit(2); } std::vector<uint8_t> v(d.begin() + (long)at, d.begin() + (long)(at + n)); at += n; return v; }
-};
 struct JobSpec { int32_t aux; std::vector<uint8_t> in; uint32_t cap; int32_t status; uint32_t pinned, out_len; int32_t aux_out; uint32_t consumed; std::vector<uint8_t> want; };
 struct Buf { uint8_t* raw; size_t mis, room, alloc, end; };
 
@@ -118,15 +100,7 @@ int check_place() {
 // unit), u32 expected out_len, i32 expected aux, u32 expected in_consumed, u32 length + the bytes the job must leave at its `out`.
 int main(int argc, char** argv) {
     if (argc != 2) { fprintf(stderr, "usage: %s CASES\n", argv[0]); return 2; }
-    Reader r;
-    {
-        FILE* f = fopen(argv[1], "rb");
-        if (!f) { perror(argv[1]); return 2; }
-        uint8_t buf[65536];
-        size_t k;
-        while ((k = fread(buf, 1, sizeof buf, f)) > 0) r.d.insert(r.d.end(), buf, buf + k);
-        fclose(f);
-    }
+    Reader r(argv[1]);
     int bad = check_place();
     const uint32_t ncases = r.u32();
     for (uint32_t c = 0; c < ncases; c++) {

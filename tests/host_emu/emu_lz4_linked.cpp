@@ -1,14 +1,12 @@
 // emu_lz4_linked.cpp -- TEST INFRASTRUCTURE.  The LZ4 path for jobs with history -- the parse with history (csrc/lz4_wave.h), the
 // copier with history (csrc/lz_copy.h) and the chain walk (csrc/lz4_chain.h) -- compiled for the HOST (g++ -DSWC_HOST_EMULATION):
-// the three steps of a launch one after the other, as kernels.hip issues them.  Never shipped.
+// the three steps of a launch one after the other, as kernels.hip issues them.  Part of libswc_emu.so (emu.cpp includes it).  Never
+// shipped.
 //
 // With -DEMU_LZ4_LINKED_MAIN the file is a stand-alone program (for -fsanitize=address,undefined): it reads chains and what the
 // oracle says about them from a file written by tests/test_lz4_linked_emulation.py, runs every chain at the sixteen alignments
 // of its buffer in the three lane orders, in allocations of exactly the size the contract asks for, and compares.
-#include <vector>
-#include <cstring>
-#include <cstdio>
-#include <cstdlib>
+#include "emu_util.h"
 #include "../../swcompression_amd/csrc/lz4_lane.h"
 #include "../../swcompression_amd/csrc/lz4_chain.h"
 
@@ -19,8 +17,6 @@ struct Areas {
     size_t bytes(uint32_t g) const { return a[g].size() - 16; }
 };
 }  // namespace
-
-extern "C" void emu_set_order(int o) { swc::simt::g_order = o; }
 
 // One launch of SWC_CODEC_LZ4_BLOCK with a workspace: lane decoder | parse | chain copy, each over all jobs.
 extern "C" void emu_lz4_linked(swc::Job* jobs, size_t n) {
@@ -50,12 +46,6 @@ extern "C" void emu_lz4_linked(swc::Job* jobs, size_t n) {
 
 #ifdef EMU_LZ4_LINKED_MAIN
 namespace {
-struct Reader {
-    std::vector<uint8_t> d;
-    size_t at = 0;
-    uint32_t u32() { uint32_t v; if (at + 4 > d.size()) { fprintf(stderr, "case file too short\n"); exit(2); } memcpy(&v, d.data() + at, 4); at += 4; return v; }
-    std::vector<uint8_t> bytes(size_t n) { if (at + n > d.size()) { fprintf(stderr, "case file too short\n"); exit(2); } std::vector<uint8_t> v(d.begin() + (long)at, d.begin() + (long)(at + n)); at += n; return v; }
-};
 struct JobSpec { int32_t aux; std::vector<uint8_t> in; uint32_t cap; int32_t status; uint32_t out_len; };
 }  // namespace
 
@@ -63,15 +53,7 @@ struct JobSpec { int32_t aux; std::vector<uint8_t> in; uint32_t cap; int32_t sta
 // u32 capacity, i32 expected status, u32 expected out_len; then u32 length + the bytes the chain must leave behind the prefix.
 int main(int argc, char** argv) {
     if (argc != 2) { fprintf(stderr, "usage: %s CASES\n", argv[0]); return 2; }
-    Reader r;
-    {
-        FILE* f = fopen(argv[1], "rb");
-        if (!f) { perror(argv[1]); return 2; }
-        uint8_t buf[65536];
-        size_t k;
-        while ((k = fread(buf, 1, sizeof buf, f)) > 0) r.d.insert(r.d.end(), buf, buf + k);
-        fclose(f);
-    }
+    Reader r(argv[1]);
     const uint32_t ncases = r.u32();
     int bad = 0;
     for (uint32_t c = 0; c < ncases; c++) {

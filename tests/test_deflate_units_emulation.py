@@ -41,8 +41,11 @@ def test_directed_runs(expected, order, copier, team):
     same one code longer (a plain job's status), one with a final block and bytes behind it, a unit that reaches back, a middle unit
     over capacity, empty units."""
     E.set_order(order)
-    units = [u for run in RUNS.values() for u in run]
-    got = E.run_units(units, copier=copier, team=team)
+    try:
+        units = [u for run in RUNS.values() for u in run]
+        got = E.run_units(units, copier=copier, team=team)
+    finally:
+        E.set_order(0)
     i = 0
     for name, run in RUNS.items():
         check_run(name, run, expected[name], got[i:i + len(run)])
@@ -78,7 +81,10 @@ def test_place_scan(order, rev):
     sizes = [300] * 200 + [17, 5, 9] + [40, 41] + [1, 0, 70001, 0, 1] + [5000, 10, 3]
     caps = [300] * 200 + [17, 5, 9] + [64, 64] + [1, 1, 70001, 8, 1] + [100, 10, 3]
     aux = [0] + [3] * 198 + [1] + [2, 3, 1] + [2, 1] + [2, 3, 3, 3, 1] + [0, 3, 1]
-    got = E.place(sizes, caps, aux, reversed_=rev)
+    try:
+        got = E.place(sizes, caps, aux, reversed_=rev)
+    finally:
+        E.set_order(0)
     head, at = None, 0
     for i, (out, st, n) in enumerate(got):
         assert st == 902 and n == sizes[i]
@@ -121,7 +127,10 @@ def test_long_run_across_tiles(order, copier, rev):
     E.set_order(order)
     jobs = K.long_run()
     exp = [K.expect(u) for u in jobs]
-    got = E.run_units(jobs, misalign=5, copier=copier, reversed_=rev)
+    try:
+        got = E.run_units(jobs, misalign=5, copier=copier, reversed_=rev)
+    finally:
+        E.set_order(0)
     assert [e[0] for e in exp[37:187]].count(K.CAPACITY) == 1 and exp[37 + 20][1] == 0 and exp[37 + 70][1] == 1
     for i in range(37):
         check_run("whole stream %d" % i, jobs[i:i + 1], exp[i:i + 1], got[i:i + 1])
