@@ -18,48 +18,14 @@
 #include <atomic>
 #include <vector>
 #include "swc_common.h"
-#include "inflate_lane.h"
-#include "inflate_sync.h"
-#include "lz_resolve.h"
-#include "lz_copy.h"
+#include "job_kernels.h"
 #include "deflate_place.h"
-#include "lz4_lane.h"
-#include "lz4_wave.h"
-#include "lz4_chain.h"
-#include "lz4_comp.h"
-#include "deflate_comp.h"
-#include "lzma_wave.h"
-#include "bzip2_block.h"
-#include "bzip2_team.h"
-#include "crc32_group.h"
-#include "crc32_wave.h"
-#include "crc32_tail.h"
 #include "checksum_group.h"
 #include "delta_group.h"
 #include "bgzf_pack.h"
 #include "launch.h"
 
 namespace swc {
-
-// A job's area of the workspace: equal strides, or -- `ws_off` given -- prefix-summed per-job sizes (ws_off[n] = total),
-// so that one large unit among many small ones does not size everybody's area.
-struct WsMap {
-    uint8_t* base;
-    size_t stride;
-    const uint64_t* off;
-    __device__ uint8_t* area(uint32_t g) const { return base ? base + (off ? (size_t)off[g] : (size_t)g * stride) : nullptr; }
-    __device__ size_t bytes(uint32_t g) const { return off ? (size_t)(off[g + 1] - off[g]) : stride; }
-};
-
-// Which job does workgroup `b` of an n-job launch take?  The hardware hands consecutive workgroups to the eight XCDs in turn
-// (workgroup b runs on XCD b % 8), so a job list whose cost has a period that divides 8 -- every fourth unit an incompressible
-// one, say -- would put all the expensive jobs on two XCDs and the launch would last as long as if every job were expensive
-// (measured: 192 text + 64 P-mix LZ4 blocks interleaved 3 : 1 took exactly the time of 256 P-mix blocks).  Here XCD x works
-// through the contiguous range [x n/8, (x + 1) n/8) of the list instead, in order: any eighth of the list costs about the same.
-__device__ __forceinline__ uint32_t xcd_job(uint32_t b, uint32_t n) {
-    const uint32_t per = n >> 3;
-    return b < (per << 3) ? (b & 7u) * per + (b >> 3) : b;
-}
 
 // ---- launch order: the longest jobs first ------------------------------------------------------------------------------
 // A job is one workgroup and lasts as long as its unit is big: 8,192 LZ4 blocks of 4 MiB are 1.7 rounds of the parse kernel's
@@ -166,9 +132,7 @@ __global__ __launch_bounds__(64, SWC_SYNC_WAVES_PER_SIMD) void swc_inflate_sync_
     __shared__ __attribute__((aligned(16))) inflate::SyncLds sync_lds;
     uint32_t g = job_of(order, blockIdx.x, n);
     if (g >= n) return;
-    Job job = jobs[g];
-    inflate::inflate_sync_job(job, &sync_lds, wm.area(g), wm.bytes(g), (int)threadIdx.x, kWave, prof ? prof + 32 * (size_t)g : nullptr);
-    if (threadIdx.x == 0) put_result<true>(jobs, g, job);   // (aux: SWC_DEFLATE_OPEN is an OUT bit)
+    jobk::inflate_sync<kWave>(jobs, g, wm, &sync_lds, (int)threadIdx.x, prof);
 }
 
 // Between the phases: the joined units of the launch get their place (deflate_place.h), one wavefront per tile of 64 consecutive
@@ -181,14 +145,11 @@ static void launch_deflate_place(Job* jobs, size_t n, hipStream_t stream) {
 }
 
 // Phase 2: one stream per workgroup of 512 threads, 64 KiB LDS ring (32 KiB of history + span + cells) -> 2 workgroups per CU.
-constexpr int kInflateResolveThreads = 512, kInflateRingLog2 = 16;
-constexpr uint32_t kInflateKeep = 32768;
 __global__ __launch_bounds__(kInflateResolveThreads) void swc_lz_resolve_kernel(const Job* __restrict__ jobs, uint32_t n, WsMap wm, uint64_t* prof, const uint32_t* __restrict__ order) {
     __shared__ __attribute__((aligned(16))) lzr::Lds<kInflateResolveThreads, kInflateRingLog2> lzr_lds;  // static: > 64 KiB needs no opt-in this way
     uint32_t g = job_of(order, blockIdx.x, n);
     if (g >= n) return;
-    Job job = jobs[g];
-    lzr::resolve_job<kInflateResolveThreads, kInflateRingLog2, kInflateKeep>(job, wm.area(g), wm.bytes(g), &lzr_lds, prof ? prof + 32 * (size_t)g + 16 : nullptr);
+    jobk::lz_resolve(jobs, g, wm, &lzr_lds, prof);
 }
 
 // Phase 2, record-granular (lz_copy.h): one stream per WAVEFRONT, the last few KiB of its output in an LDS window, older
@@ -203,57 +164,34 @@ __global__ __launch_bounds__(kInflateResolveThreads) void swc_lz_resolve_kernel(
 //            (9 KiB / 2 KiB groups / 16 waves: 57.9 against 56.6 ms).
 // CRC (Deflate, swc_lz_copy_crc32_kernel further down): when copy_job has returned -- on whichever path: no literal stream, no
 // records, a failed stream -- the window is dead, and the wave ends with the CRC-32 of its own output in crcs[g] (crc32_tail.h).
-constexpr uint64_t kCrcGroupLen = 1u << 20;   // CRC-32 of a stream: by one wave below, by a 256-thread group from here on
 extern __device__ crcw::WaveConsts g_crc_consts;
-template <typename CFG, int RM = 0, bool CRC = false>
-__device__ __forceinline__ void lz_copy_body(const Job* __restrict__ jobs, uint32_t n, const WsMap& wm, const uint32_t* __restrict__ order, uint32_t* __restrict__ crcs = nullptr) {
-    __shared__ __attribute__((aligned(16))) lzc::Lds<CFG::kWin> lds;
-    uint32_t g = job_of(order, blockIdx.x, n);
-    if (g >= n) return;
-    Job job = jobs[g];
-    if constexpr (!CRC) {
-        if (job.dict != nullptr) return;   // (LZ4 blocks with a dictionary prefix were decoded by the lane kernel)
-        lzc::copy_job<CFG, RM>(job, wm.area(g), wm.bytes(g), &lds);
-    } else {
-        static_assert(sizeof(crct::TailConsts) <= CFG::kWin, "the constants of the tail go where the window was");
-        if (job.dict == nullptr) lzc::copy_job<CFG, RM>(job, wm.area(g), wm.bytes(g), &lds);
-        // what swc_batch_crc32 covers; streams of a megabyte and more (the 64-bit positions among them) are left to
-        // swc_crc32_group_kernel, which the launch puts behind this kernel
-        const uint64_t len = job.out_len < job.out_cap ? job.out_len : job.out_cap;
-        if (len >= kCrcGroupLen) return;
-        simt::vmem_fence();   // every store of this wave has arrived (what drain() waits for)
-        const uint32_t c = crct::crc32_tail((gcptr)job.out, simt::uniform((uint32_t)len), (crct::TailConsts*)lds.win, &g_crc_consts);
-        if (threadIdx.x == 0) crcs[g] = c;
-    }
-}
 #ifndef SWC_LZC_WAVES
 #define SWC_LZC_WAVES 6
-#endif
-// how the LZ4 parse tells the copy kernel where a record's literals lie in the block (lz4_wave.h): 1 = eight-byte records with the
-// offset in the upper dword, 2 = four-byte records, the offset derived by a running sum, anchors where the rule breaks
-#ifndef SWC_LZ4_RECORD_MODE
-#define SWC_LZ4_RECORD_MODE 2
 #endif
 #ifndef SWC_LZC4_WAVES
 #define SWC_LZC4_WAVES 5
 #endif
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZC_WAVES, SWC_LZC_WAVES))) void swc_lz_copy_kernel(const Job* __restrict__ jobs, uint32_t n, WsMap wm, const uint32_t* __restrict__ order) {
-    lz_copy_body<lzc::CfgDeflate>(jobs, n, wm, order);
+    __shared__ __attribute__((aligned(16))) lzc::Lds<lzc::CfgDeflate::kWin> lds;
+    uint32_t g = job_of(order, blockIdx.x, n);
+    if (g >= n) return;
+    jobk::lz_copy<lzc::CfgDeflate, false>(jobs, g, wm, &lds, (int)threadIdx.x);
 }
 // LZ4: the wave of a job takes the linked jobs behind it along, one after the other (lz4_chain.h); it writes their `out` and their
 // results, so the job list is not read-only here.  only_chain: the launch's other jobs are swc_lz4_resolve_kernel's.
-__device__ __forceinline__ int32_t lz4_next_aux(const Job* jobs, uint32_t g, uint32_t n) { return g + 1u < n ? jobs[g + 1u].aux : 0; }
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZC4_WAVES, SWC_LZC4_WAVES))) void swc_lz4_copy_kernel(Job* jobs, uint32_t n, WsMap wm, const uint32_t* __restrict__ order, int only_chain) {
     __shared__ __attribute__((aligned(16))) lzc::Lds<lzc::CfgLz4::kWin> lds;
     uint32_t g = job_of(order, blockIdx.x, n);
     if (g >= n) return;
-    if (only_chain && !lz4w::chain_job(jobs[g], lz4_next_aux(jobs, g, n))) return;
-    lz4w::copy_chain<lzc::CfgLz4, SWC_LZ4_RECORD_MODE>(jobs, g, n, wm, &lds);   // (the literals come from the block itself)
+    jobk::lz4_copy(jobs, g, n, wm, &lds, only_chain);
 }
 // The Deflate copy kernel that ends with the stream's CRC-32: the same body, the same window, the same 24 waves per CU.  A kernel
 // of its own, so that swc_lz_copy_kernel keeps its instructions and its 40 VGPRs (the tail holds four rows of the stream in flight).
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZC_WAVES, SWC_LZC_WAVES))) void swc_lz_copy_crc32_kernel(const Job* __restrict__ jobs, uint32_t n, WsMap wm, const uint32_t* __restrict__ order, uint32_t* __restrict__ crcs) {
-    lz_copy_body<lzc::CfgDeflate, 0, true>(jobs, n, wm, order, crcs);
+    __shared__ __attribute__((aligned(16))) lzc::Lds<lzc::CfgDeflate::kWin> lds;
+    uint32_t g = job_of(order, blockIdx.x, n);
+    if (g >= n) return;
+    jobk::lz_copy<lzc::CfgDeflate, true>(jobs, g, wm, &lds, (int)threadIdx.x, crcs, &g_crc_consts);
 }
 // "lz_copier" (swc_set_tuning): 1 = lz_copy.h with the windows above (default), 0 = the byte-cell resolver of lz_resolve.h
 // (rounds 2-4) -- both produce the same bytes.
@@ -375,16 +313,7 @@ hipError_t launch_inflate(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStr
 __global__ __launch_bounds__(64) void swc_lz4_lane_kernel(Job* __restrict__ jobs, uint32_t n, int only_dict) {
     uint32_t g = blockIdx.x * kWave + threadIdx.x;
     if (g >= n) return;
-    Job job = jobs[g];
-    if (only_dict) {
-        if (!lz4w::lane_job(job)) return;
-    } else if ((job.aux & (kLz4Linked | kLz4Stored)) != 0) {   // (no workspace: nowhere to leave the records of a chain)
-        job.status = SWC_E_NEED_WORKSPACE; job.out_len = 0; job.in_consumed = 0;
-        put_result(jobs, g, job);
-        return;
-    }
-    lz4::lz4_block_job(job);
-    put_result(jobs, g, job);
+    jobk::lz4_lane(jobs, g, only_dict);
 }
 
 #ifndef SWC_LZ4_PARSE_WAVES
@@ -398,23 +327,15 @@ template <int RM>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZ4_PARSE_WAVES))) void swc_lz4_parse_kernel(Job* __restrict__ jobs, uint32_t n, WsMap wm, uint64_t* prof, const uint32_t* __restrict__ order, int which) {
     uint32_t g = job_of(order, blockIdx.x, n);
     if (g >= n) return;
-    Job job = jobs[g];
-    if (lz4w::lane_job(job)) return;
-    if (which != 0 && lz4w::chain_job(job, lz4_next_aux(jobs, g, n)) != (which == 1)) return;
     __shared__ __attribute__((aligned(16))) uint8_t stage[lz4w::kStageLds];
-    uint64_t hist = 0;
-    if (RM == 0 || !lz4w::parse_preset(job, hist))
-        lz4w::lz4_parse_job<kWave, RM>(job, wm.area(g), wm.bytes(g), (int)threadIdx.x, stage, prof ? prof + 32 * (size_t)g : nullptr, RM == 0 ? 0u : hist);
-    if (threadIdx.x == 0) put_result(jobs, g, job);
+    jobk::lz4_parse<kWave, RM>(jobs, g, n, wm, stage, (int)threadIdx.x, prof, which);
 }
 
 __global__ __launch_bounds__(lz4w::kResolveThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void swc_lz4_resolve_kernel(const Job* __restrict__ jobs, uint32_t n, WsMap wm, uint64_t* prof, const uint32_t* __restrict__ order) {
     __shared__ __attribute__((aligned(16))) lzr::Lds<lz4w::kResolveThreads, lz4w::kRingLog2> lds;
     uint32_t g = job_of(order, blockIdx.x, n);
     if (g >= n) return;
-    Job job = jobs[g];
-    if (lz4w::lane_job(job) || lz4w::chain_job(job, lz4_next_aux(jobs, g, n))) return;
-    lzr::resolve_job<lz4w::kResolveThreads, lz4w::kRingLog2, lz4w::kKeep, true>(job, wm.area(g), wm.bytes(g), &lds, prof ? prof + 32 * (size_t)g + 16 : nullptr);
+    jobk::lz4_resolve(jobs, g, n, wm, &lds, prof);
 }
 
 size_t lz4_ws_bytes_per_job(uint64_t cap) { return lzr::ws_bytes_per_job(cap); }
@@ -455,9 +376,7 @@ __global__ __launch_bounds__(64) void swc_lz4_compress_kernel(Job* __restrict__ 
     __shared__ __attribute__((aligned(16))) uint16_t table[lz4c::kHashSize];
     uint32_t g = job_of(order, blockIdx.x, n);
     if (g >= n) return;
-    Job job = jobs[g];
-    lz4c::lz4_compress_job<kWave>(job, table);
-    if (threadIdx.x == 0) put_result(jobs, g, job);
+    jobk::lz4_compress<kWave>(jobs, g, table, (int)threadIdx.x);
 }
 hipError_t launch_lz4_compress(Job* jobs, size_t n, hipStream_t stream) {
     if (n == 0) return hipSuccess;
@@ -473,9 +392,7 @@ __global__ __launch_bounds__(64) void swc_deflate_compress_kernel(Job* __restric
     __shared__ __attribute__((aligned(16))) defc::Lds lds;
     uint32_t g = job_of(order, blockIdx.x, n);
     if (g >= n) return;
-    Job job = jobs[g];
-    defc::deflate_compress_job<kWave>(job, &lds);
-    if (threadIdx.x == 0) put_result(jobs, g, job);
+    jobk::deflate_compress<kWave>(jobs, g, &lds, (int)threadIdx.x);
 }
 hipError_t launch_deflate_compress(Job* jobs, size_t n, hipStream_t stream) {
     if (n == 0) return hipSuccess;
@@ -491,9 +408,7 @@ __global__ __launch_bounds__(64) void swc_deflate_compress_dynamic_kernel(Job* _
     __shared__ __attribute__((aligned(16))) defc::DynLds lds;
     uint32_t g = job_of(order, blockIdx.x, n);
     if (g >= n) return;
-    Job job = jobs[g];
-    defc::deflate_compress_dynamic_job<kWave>(job, &lds);
-    if (threadIdx.x == 0) put_result(jobs, g, job);
+    jobk::deflate_compress_dynamic<kWave>(jobs, g, &lds, (int)threadIdx.x);
 }
 hipError_t launch_deflate_compress_dynamic(Job* jobs, size_t n, hipStream_t stream) {
     if (n == 0) return hipSuccess;
@@ -509,8 +424,7 @@ hipError_t launch_deflate_compress_dynamic(Job* jobs, size_t n, hipStream_t stre
 // kernel keeps literal coders up to lc + lp = 3 in LDS -- what xz writes -- which is 15,984 B per wave = 10 streams per
 // CU; streams with lc + lp > 3 then run their literal coder out of HBM.  Without a workspace lc + lp = 4 still fits in
 // LDS (28,272 B, 5 streams per CU) and only lc + lp > 4 (legal for .lzma, never produced by xz) reports
-// SWC_E_NEED_WORKSPACE.  `spill` holds kLzmaSpillBytes per job.
-constexpr size_t kLzmaSpillBytes = (size_t)(0x300u << 12) * 2 + 1024;   // every literal coder of lc + lp <= 12, then the two `high` length trees
+// SWC_E_NEED_WORKSPACE.  `spill` holds kLzmaSpillBytes per job (job_kernels.h).
 
 // LDSBITS >= 0: the literal coders of lc + lp <= LDSBITS in LDS (no workspace: 4 -> 28 KB, 5 streams per CU);
 // LDSBITS < 0: LDS as a cache of kCoderSlots literal coders (one: 5,232 B, 31 streams per CU), all of them in the workspace (lzma_wave.h)
@@ -522,10 +436,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZMA_WAV
     extern __shared__ __attribute__((aligned(16))) uint16_t lzma_lds[];
     uint32_t g = xcd_job(blockIdx.x, n);
     if (g >= n) return;
-    Job job = jobs[g];
-    SWC_AS_GLOBAL uint16_t* sp = spill ? (SWC_AS_GLOBAL uint16_t*)(spill + (size_t)g * kLzmaSpillBytes) : nullptr;
-    lzma::lzma_job<kWave>(job, LZMA2, lzma_lds, sp, (int)threadIdx.x, LDSBITS < 0 ? 0 : LDSBITS, prof ? prof + 32 * (size_t)g : nullptr, LDSBITS < 0);
-    if (threadIdx.x == 0) put_result(jobs, g, job);
+    jobk::lzma_stream<kWave, LZMA2, LDSBITS>(jobs, g, spill, lzma_lds, (int)threadIdx.x, prof);
 }
 
 size_t lzma_spill_bytes_per_job() { return kLzmaSpillBytes; }
@@ -558,9 +469,7 @@ hipError_t launch_lzma(bool lzma2, Job* jobs, size_t n, void* spill, hipStream_t
 // share), stage 2 (counting-sort scatter) and stage 3a (the segmented walk of the BWT cycle: bound by the latency of
 // random HBM accesses) back to back.  As separate launches the three ran one after the other, each limited by its own
 // resource while the others idled; in one kernel the waves of a CU are at different stages at any time, so the scalar
-// work of some overlaps the memory waits of the others.  LDS: the three stages' areas share one allocation.
-constexpr size_t kBzLdsBytes = bzip2::kStage1LdsBytes > sizeof(bzip2::Stage3Lds) ? (size_t)bzip2::kStage1LdsBytes : sizeof(bzip2::Stage3Lds);
-static_assert(kBzLdsBytes >= 256 * sizeof(uint32_t), "stage 2 counters");
+// work of some overlaps the memory waits of the others.  LDS: the three stages' areas share one allocation (kBzLdsBytes).
 #ifndef SWC_BZ_WAVES
 #define SWC_BZ_WAVES 6   // (round 4, stage 3 inside: 7 -> 72 VGPRs + 8 bytes of scratch, 495 ms against 479; round 6, stages 1 + 2 only: 6 / 7 / 8 -> 198.4 / 200.3 / 199.4 ms)
 #endif
@@ -572,15 +481,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_BZ_WAVES
     __shared__ __attribute__((aligned(16))) uint8_t bz_lds[kBzLdsBytes];
     uint32_t g = xcd_job(blockIdx.x, n);
     if (g >= n) return;
-    Job job = jobs[g];
-    const bzip2::Workspace w = bzip2::carve(ws, g, lcap);
-    bzip2::stage1_job<kWave, CXX>(job, reinterpret_cast<bzip2::Stage1Lds*>(bz_lds), w, (int)threadIdx.x);
-    __threadfence_block();   // L and the block header, written by some lanes, are read by all of them from here on
-    bzip2::stage2_job(w, reinterpret_cast<uint32_t*>(bz_lds));
-    if (team) return;
-    __threadfence_block();   // likewise the pointer array P
-    bzip2::stage3_walk_job<kWave>(job, w, reinterpret_cast<bzip2::Stage3Lds*>(bz_lds), (int)threadIdx.x);
-    if (threadIdx.x == 0 && !bzip2::stage3_expand_needed(w)) put_result<true>(jobs, g, job);
+    jobk::bzip2_block<kWave, CXX>(jobs, g, ws, lcap, bz_lds, (int)threadIdx.x, team);
 }
 
 // ---- stage 3a as kernels of its own (bzip2_team.h) ------------------------------------------------------------------------------
@@ -599,21 +500,14 @@ __global__ __launch_bounds__(64) void swc_bzip2_team_finish_kernel(Job* __restri
     __shared__ bzip2::FinishLds lds;
     uint32_t g = xcd_job(blockIdx.x, n);
     if (g >= n) return;
-    Job job = jobs[g];
-    const bzip2::Workspace w = bzip2::carve(ws, g, lcap);
-    bzip2::team_finish<kWave>(job, w, &lds, (int)threadIdx.x);
-    if (threadIdx.x == 0 && !bzip2::stage3_expand_needed(w)) put_result<true>(jobs, g, job);
+    jobk::bzip2_team_finish<kWave>(jobs, g, ws, lcap, &lds, (int)threadIdx.x);
 }
 
 // stage 3b: one block per lane, only what stage 3a could not finish (serial walk + RLE1 undo)
 __global__ __launch_bounds__(64) void swc_bzip2_expand_kernel(Job* __restrict__ jobs, uint32_t n, uint8_t* ws, size_t lcap) {
     uint32_t g = blockIdx.x * kWave + threadIdx.x;
     if (g >= n) return;
-    const bzip2::Workspace w = bzip2::carve(ws, g, lcap);
-    if (!bzip2::stage3_expand_needed(w)) return;
-    Job job = jobs[g];
-    bzip2::stage3_expand_job(job, w);
-    put_result<true>(jobs, g, job);
+    jobk::bzip2_expand(jobs, g, ws, lcap);
 }
 
 // stage 3c: one block per workgroup (block CRC, BZip2.swift:81)
@@ -679,7 +573,7 @@ hipError_t launch_bzip2(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStrea
 // Two kernels, both launched over all n jobs, each taking the jobs of its size class (the sizes are on the device; a wave or
 // group whose job belongs to the other kernel ends at once): one stream per WAVE below 1 MB (crc32_wave.h: no per-stream
 // set-up, no barrier after the constants are in LDS), one stream per 256-thread group above (crc32_group.h).
-__device__ crcw::WaveConsts g_crc_consts;   // (kCrcGroupLen: above lz_copy_body, whose tail takes the streams below it)
+__device__ crcw::WaveConsts g_crc_consts;   // (kCrcGroupLen: job_kernels.h, where the copy kernel's tail takes the streams below it)
 __global__ __launch_bounds__(256) void swc_crc32_consts_kernel() { crcw::build_consts<256>(&g_crc_consts, (int)threadIdx.x); }
 
 __global__ __launch_bounds__(256) void swc_crc32_kernel(const Job* __restrict__ jobs, uint32_t n, uint32_t* __restrict__ crcs) {
@@ -693,10 +587,7 @@ __global__ __launch_bounds__(256) void swc_crc32_kernel(const Job* __restrict__ 
     __syncthreads();
     const uint32_t g = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (g >= n) return;
-    const uint64_t len = jobs[g].out_len < jobs[g].out_cap ? jobs[g].out_len : jobs[g].out_cap;
-    if (len >= kCrcGroupLen) return;
-    const uint32_t c = crcw::crc32_wave((gcptr)jobs[g].out, simt::uniform(len), &lds);
-    if ((threadIdx.x & 63) == 0) crcs[g] = c;
+    jobk::crc32_wave(jobs, g, crcs, &lds, (int)(threadIdx.x & 63));
 }
 
 // A fixed number of groups, each looking after a contiguous range of jobs: one parallel read of the lengths, then the streams
@@ -713,14 +604,14 @@ __global__ __launch_bounds__(256) void swc_crc32_group_kernel(const Job* __restr
         __syncthreads();
         const uint32_t g = base + threadIdx.x;
         if (g < hi) {
-            const uint64_t len = jobs[g].out_len < jobs[g].out_cap ? jobs[g].out_len : jobs[g].out_cap;
+            const uint64_t len = made_bytes(jobs[g].out_len, jobs[g].out_cap);
             if (len >= kCrcGroupLen) big[atomicAdd(&nbig, 1u)] = g;
         }
         __syncthreads();
         const uint32_t cnt = nbig;
         for (uint32_t i = 0; i < cnt; i++) {
             const uint32_t j = big[i];
-            const uint64_t len = jobs[j].out_len < jobs[j].out_cap ? jobs[j].out_len : jobs[j].out_cap;
+            const uint64_t len = made_bytes(jobs[j].out_len, jobs[j].out_cap);
             const uint32_t c = crc::crc32_group<256>((gcptr)jobs[j].out, len, &lds, (int)threadIdx.x);
             if (threadIdx.x == 0) crcs[j] = c;
             __syncthreads();
@@ -795,7 +686,7 @@ __global__ __launch_bounds__(256) void swc_crc_kernel(const Job* __restrict__ jo
     __shared__ crc::Lds<256, W> lds;
     uint32_t g = xcd_job(blockIdx.x, n);
     if (g >= n) return;
-    const uint64_t len = jobs[g].out_len < jobs[g].out_cap ? jobs[g].out_len : jobs[g].out_cap;
+    const uint64_t len = made_bytes(jobs[g].out_len, jobs[g].out_cap);
     W c = crc::crc_group<256, W, MSB>((gcptr)jobs[g].out, len, &lds, (int)threadIdx.x);
     if (threadIdx.x == 0) sums[g] = (uint64_t)c;
 }
@@ -804,7 +695,7 @@ __global__ __launch_bounds__(256) void swc_adler32_kernel(const Job* __restrict_
     __shared__ sums::AdlerLds<256> lds;
     uint32_t g = xcd_job(blockIdx.x, n);
     if (g >= n) return;
-    const uint64_t len = jobs[g].out_len < jobs[g].out_cap ? jobs[g].out_len : jobs[g].out_cap;
+    const uint64_t len = made_bytes(jobs[g].out_len, jobs[g].out_cap);
     uint32_t c = sums::adler32_group<256>((gcptr)jobs[g].out, len, &lds, (int)threadIdx.x);
     if (threadIdx.x == 0) sums[g] = c;
 }
@@ -815,7 +706,7 @@ __global__ __launch_bounds__(64) void swc_xxh32_kernel(const Job* __restrict__ j
     const int j = (int)(threadIdx.x & 3);
     const bool live = g < n;
     gcptr out = live ? (gcptr)jobs[g].out : nullptr;
-    const uint64_t len = live ? (jobs[g].out_len < jobs[g].out_cap ? jobs[g].out_len : jobs[g].out_cap) : 0;
+    const uint64_t len = live ? made_bytes(jobs[g].out_len, jobs[g].out_cap) : 0;
     auto quad_get = [](uint32_t v, int k) -> uint32_t {
         switch (k) {   // quad_perm broadcasts
             case 0: return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x00, 0xf, 0xf, false);

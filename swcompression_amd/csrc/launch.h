@@ -1,4 +1,5 @@
-// launch.h -- host-side launch wrappers implemented in kernels.hip.
+// launch.h -- host-side launch wrappers implemented in kernels.hip (launch_inflate_team: inflate_team.hip): which kernels, in which
+// order, with which flags.  What a kernel does with its job is in job_kernels.h.
 #ifndef SWC_LAUNCH_H
 #define SWC_LAUNCH_H
 #include <hip/hip_runtime.h>

@@ -59,6 +59,7 @@ SWC_D void copy_chain(Job* jobs, uint32_t g, uint32_t n, const WS& wm, lzc::Lds<
     uint8_t* next_out = job.out;
     for (uint32_t j = g;;) {
         const bool head = j == g;
+        SWC_LZ4_STAT(5, 1);
         if (head) {
             if (adjacent_prefix(job)) prefix = job.dict_len;
         } else {

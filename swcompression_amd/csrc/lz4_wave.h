@@ -78,8 +78,9 @@ enum { kLzStop = 1u, kLzFail = 2u, kLzTrap = 4u, kLzTail = 8u, kLzLong = 16u };
 #define SWC_LP(k)
 #endif
 #if defined(SWC_HOST_EMULATION)
-inline uint64_t g_lz4_stats[8];   // emulated parser: rounds, lane parses, passes, sequences taken by rounds, checked steps
-#define SWC_LZ4_STAT(i, n) (g_lz4_stats[i] += (n))
+inline uint64_t g_lz4_stats[8];   // emulated parser: rounds, lane parses, passes, sequences taken by rounds, checked steps,
+                                   // [5] jobs a decoding path took: the lane decoder, the resolver, a chain copier's wave (job_kernels.h)
+#define SWC_LZ4_STAT(i, n) (::swc::lz4w::g_lz4_stats[i] += (n))
 #else
 #define SWC_LZ4_STAT(i, n) ((void)0)
 #endif

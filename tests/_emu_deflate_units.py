@@ -32,11 +32,11 @@ def place(sizes, caps, aux, base=0x10000, reversed_=False):
     return [(jobs[i].out or 0, jobs[i].status, jobs[i].out_len) for i in range(n)]
 
 
-def run_units(units, misalign=0, copier=1, team=0, reversed_=False, head_gap=None):
+def run_units(units, misalign=0, copier=1, team=0, reversed_=False, head_gap=None, crcs=None):
     """One emulated launch.  units: list of dicts data / cap / aux.  Every job that is not joined starts a buffer of its own -- the sum
     of its run's capacities, `misalign` bytes past a 16-byte boundary, GUARD bytes of 0xA5 on both sides.  Returns per job (status,
     out_len, in_consumed, aux, offset of `out` from its head's, bytes); asserts that every guard is intact and that nothing behind
-    the last byte a run produced was written."""
+    the last byte a run produced was written.  crcs: a (c_uint32 * n) array that the launch leaves as one with CRCs does."""
     n = len(units)
     jobs = (Job * n)()
     keep, bufs, head_of = [], {}, []
@@ -58,7 +58,7 @@ def run_units(units, misalign=0, copier=1, team=0, reversed_=False, head_gap=Non
             if not (u["aux"] & JOINED):
                 jobs[i].out = bufs[i].addr
         head_of.append(max(k for k in bufs if k <= i))
-    lib.emu_deflate_units(jobs, C.c_size_t(n), C.c_int(copier), C.c_int(team), C.c_int(1 if reversed_ else 0))
+    lib.emu_deflate_units(jobs, C.c_size_t(n), C.c_int(copier), C.c_int(team), C.c_int(1 if reversed_ else 0), crcs)
     res = []
     used = {h: 0 for h in bufs}
     for i in range(n):

@@ -2,80 +2,21 @@
 // (g++ -DSWC_HOST_EMULATION): the uniform parts run once, the threads of every SIMT region (csrc/simt.h) one
 // after another in a selectable order.  Lets the CPU-only test tier exercise
 // the exact source the gfx950 kernels are compiled from against the oracle.  Never shipped, never
-// linked into libswc_hip.so.  This file is the whole library: the drivers of the later features (emu_bgzf.cpp, emu_crc_tail.cpp,
-// emu_lz4_linked.cpp, emu_deflate_units.cpp) are included at its end, so that one compile shares the template instantiations.
+// linked into libswc_hip.so.  A driver that emulates a launch calls the kernel bodies of csrc/job_kernels.h -- what the __global__
+// functions call -- in the order the launcher issues the kernels; the other entry points test one header function alone.  This
+// file is the whole library: the drivers that have a source of their own (emu_bgzf.cpp, emu_crc_tail.cpp, emu_lz4_linked.cpp --
+// every LZ4 decode launch --, emu_deflate_units.cpp -- every Deflate decode launch) are included at its end, so that one compile
+// shares the template instantiations.
 #include <algorithm>
 #include <memory>
 #include "emu_util.h"
-#include "../../swcompression_amd/csrc/inflate_lane.h"
-#include "../../swcompression_amd/csrc/inflate_sync.h"
-#include "../../swcompression_amd/csrc/lz4_lane.h"
-#include "../../swcompression_amd/csrc/lz4_wave.h"
-#include "../../swcompression_amd/csrc/lz4_comp.h"
-#include "../../swcompression_amd/csrc/deflate_comp.h"
 #include "../../swcompression_amd/csrc/huffman_wave.h"
-#include "../../swcompression_amd/csrc/lz_copy.h"
-#include "../../swcompression_amd/csrc/lzma_wave.h"
-#include "../../swcompression_amd/csrc/bzip2_block.h"
-#include "../../swcompression_amd/csrc/bzip2_team.h"
 #include "../../swcompression_amd/csrc/bzip2_comp.h"
-#include "../../swcompression_amd/csrc/crc32_group.h"
 
-// phase 2: 1 = the record-granular copier of lz_copy.h as the library ships it (Deflate: 6 KiB window, LZ4: 7 KiB), 3 = the 6 KiB
-// window for both, 2 = the 7 KiB window for both, 0 = the byte-cell resolver of lz_resolve.h
-static int g_copier = 1;
-extern "C" void emu_set_copier(int on) { g_copier = on; }
-// (the two window configurations the library ships: kernels.hip)
+// phase 2 alone on a workspace area a test has laid out (emu_copy_records*): lz_copy.h in either window
 template <typename CFG, int RM = 0>
 static void emu_copy(swc::Job& job, const uint8_t* ws, size_t wsb) {
-    alignas(16) static swc::lzc::Lds<CFG::kWin> cl;
-    std::memset(&cl, 0xEE, sizeof cl);
-    swc::lzc::copy_job<CFG, RM>(job, ws, wsb, &cl);
-}
-// how the LZ4 parse tells the copier where the literals lie (kernels.hip: SWC_LZ4_RECORD_MODE): 1 = eight-byte records, 2 = derived + anchors
-static int g_lz4_mode = 2;
-extern "C" void emu_set_lz4_record_mode(int m) { g_lz4_mode = m; }
-// (Deflate: four-byte records + the dense literal stream; LZ4: eight-byte records whose literals stay in the block -- R8)
-static void emu_copy_any(int deflate, swc::Job& job, const uint8_t* ws, size_t wsb) {
-    if (deflate) {
-        if (g_copier == 2) emu_copy<swc::lzc::CfgLz4>(job, ws, wsb);
-        else emu_copy<swc::lzc::CfgDeflate>(job, ws, wsb);
-    } else {
-        if (g_lz4_mode == 1) {
-            if (g_copier == 3) emu_copy<swc::lzc::CfgDeflate, 1>(job, ws, wsb);
-            else emu_copy<swc::lzc::CfgLz4, 1>(job, ws, wsb);
-        } else {
-            if (g_copier == 3) emu_copy<swc::lzc::CfgDeflate, 2>(job, ws, wsb);
-            else emu_copy<swc::lzc::CfgLz4, 2>(job, ws, wsb);
-        }
-    }
-}
-
-// Deflate, one stream per wavefront with 64 sub-chunks decoded at once (inflate_sync.h): the uniform parts run once, the
-// 64 lanes of every parallel region one after another (csrc/simt.h).
-// phase 1 with a team of wavefronts per stream (inflate_sync.h; kernels.hip: launches of few streams): 0 = one wavefront
-static int g_team = 0;
-extern "C" void emu_set_deflate_team(int on) { g_team = on; }
-extern "C" uint64_t emu_team_adopted(int reset) { const uint64_t v = swc::inflate::g_team_adopted; if (reset) swc::inflate::g_team_adopted = 0; return v; }
-extern "C" void emu_inflate_sync(swc::Job* jobs, size_t n) {
-    alignas(16) static swc::inflate::SyncLds sl;
-    alignas(16) static swc::lzr::Lds<512, 16> rl;
-    for (size_t g = 0; g < n; g++) {
-        std::memset(&sl, 0xEE, sizeof sl);
-        size_t wsb = swc::lzr::ws_bytes_per_job(jobs[g].out_cap);
-        std::vector<uint8_t> ws(wsb + 16, (uint8_t)0xCD);
-        if (g_team) {
-            EmuTeam t;
-            swc::inflate::inflate_sync_job<true>(jobs[g], t.tm.lds, ws.data(), wsb, 0, 1, nullptr, &t.tm);
-        } else
-        swc::inflate::inflate_sync_job(jobs[g], &sl, ws.data(), wsb, 0, 1);
-        if (g_copier) {
-            emu_copy_any(1, jobs[g], ws.data(), wsb);
-            continue;
-        }
-        std::memset(&rl, 0xEE, sizeof rl);
-        swc::lzr::resolve_job<512, 16, 32768>(jobs[g], ws.data(), wsb, &rl);
-    }
+    swc::lzc::copy_job<CFG, RM>(job, ws, wsb, emu_lds<swc::lzc::Lds<CFG::kWin>>());
 }
 
 extern "C" void emu_lz4_stats(uint64_t* out, int reset) {
@@ -86,53 +27,19 @@ extern "C" void emu_sync_stats(uint64_t* out, int reset) {
     for (int i = 0; i < 8; i++) { out[i] = swc::inflate::g_sync_stats[i]; if (reset) swc::inflate::g_sync_stats[i] = 0; }
 }
 
-// LZ4: blocks with a dictionary prefix on the lane decoder, the others through the two-phase path (parse with a
-// one-lane "wavefront", resolve with a one-thread "workgroup").
-extern "C" void emu_lz4_block(swc::Job* jobs, size_t n) {
-    alignas(16) static swc::lzr::Lds<swc::lz4w::kResolveThreads, swc::lz4w::kRingLog2> rl;
-    for (size_t g = 0; g < n; g++) {
-        if (jobs[g].dict) { swc::lz4::lz4_block_job(jobs[g]); continue; }
-        size_t wsb = swc::lzr::ws_bytes_per_job(jobs[g].out_cap);
-        std::vector<uint8_t> ws(wsb + 16, (uint8_t)0xCD);
-        alignas(16) static uint8_t stage[swc::lz4w::kStageLds];
-        std::memset(stage, 0xEE, sizeof stage);
-        if (g_copier) {
-            if (g_lz4_mode == 1) swc::lz4w::lz4_parse_job<1, 1>(jobs[g], ws.data(), wsb, 0, stage);
-            else swc::lz4w::lz4_parse_job<1, 2>(jobs[g], ws.data(), wsb, 0, stage);
-            emu_copy_any(0, jobs[g], ws.data(), wsb);
-            continue;
-        }
-        swc::lz4w::lz4_parse_job<1>(jobs[g], ws.data(), wsb, 0, stage);
-        std::memset(&rl, 0xEE, sizeof rl);
-        swc::lzr::resolve_job<swc::lz4w::kResolveThreads, swc::lz4w::kRingLog2, swc::lz4w::kKeep, true>(jobs[g], ws.data(), wsb, &rl);
-    }
-}
-
 // LZ4 block compression (lz4_comp.h): job.in = prefix ++ block, job.dict_len = length of the prefix
 extern "C" void emu_lz4_compress(swc::Job* jobs, size_t n) {
-    alignas(16) static uint16_t table[swc::lz4c::kHashSize];
-    for (size_t g = 0; g < n; g++) {
-        std::memset(table, 0xEE, sizeof table);
-        swc::lz4c::lz4_compress_job<64>(jobs[g], table);
-    }
+    for (size_t g = 0; g < n; g++) swc::jobk::lz4_compress<64>(jobs, (uint32_t)g, emu_lds<std::array<uint16_t, swc::lz4c::kHashSize>>()->data(), 0);
 }
 
 // Deflate compression (deflate_comp.h): job.in = the buffer
 extern "C" void emu_deflate_compress(swc::Job* jobs, size_t n) {
-    alignas(16) static swc::defc::Lds lds;
-    for (size_t g = 0; g < n; g++) {
-        std::memset(&lds, 0xEE, sizeof lds);
-        swc::defc::deflate_compress_job<64>(jobs[g], &lds);
-    }
+    for (size_t g = 0; g < n; g++) swc::jobk::deflate_compress<64>(jobs, (uint32_t)g, emu_lds<swc::defc::Lds>(), 0);
 }
 
 // Deflate compression with dynamic blocks: job.in = the buffer, job.aux bit 0 = a segment of a longer stream
 extern "C" void emu_deflate_compress_dynamic(swc::Job* jobs, size_t n) {
-    alignas(16) static swc::defc::DynLds lds;
-    for (size_t g = 0; g < n; g++) {
-        std::memset(&lds, 0xEE, sizeof lds);
-        swc::defc::deflate_compress_dynamic_job<64>(jobs[g], &lds);
-    }
+    for (size_t g = 0; g < n; g++) swc::jobk::deflate_compress_dynamic<64>(jobs, (uint32_t)g, emu_lds<swc::defc::DynLds>(), 0);
 }
 
 // the shared builder on its own: weights w[0 .. alpha) (alpha <= 288) -> code lengths and canonical codes (MSB first)
@@ -148,36 +55,40 @@ extern "C" void emu_huffman(const uint32_t* w, uint32_t alpha, uint32_t max_len,
 // spill (lc+lp > 4) is always available, as the single-shot C ABI guarantees on the device.
 // mode 0: every literal coder in LDS up to lc + lp = 4, larger models cell by cell from the spill (the kernel without a
 // workspace, and the old spill path); mode 1: LDS as a cache of kCoderSlots literal coders, long-length trees in the spill (the kernel with a workspace).
-extern "C" void emu_lzma_mode(swc::Job* jobs, size_t n, int is_lzma2, int mode) {
+// TEST-ONLY choices of the kernel's template arguments: mode 0 is swc_lzma_kernel<LZMA2, 4> WITH a spill buffer, which launch_lzma
+// hands that instantiation never (it gets nullptr), and <LZMA2, 3> -- launch_lzma's choice with a workspace and the cache off -- is not run here.
+template <bool LZMA2, int LDSBITS>
+static void emu_lzma_launch(swc::Job* jobs, size_t n) {
     std::vector<uint16_t> probs(swc::lzma::kProbCells + 8);
-    std::vector<uint16_t> spill(((size_t)0x300 << 12) + 512);   // (+ the two `high` length trees of the cache mode)
+    std::vector<uint16_t> spill(swc::kLzmaSpillBytes / 2);
     for (size_t g = 0; g < n; g++) {
         std::fill(probs.begin(), probs.end(), (uint16_t)0xBEEF);
         std::fill(spill.begin(), spill.end(), (uint16_t)0xDEAD);
-        swc::lzma::lzma_job<1>(jobs[g], is_lzma2 != 0, probs.data(), spill.data(), 0, swc::lzma::kMaxLdsLitBits, nullptr, mode == 1);
+        swc::jobk::lzma_stream<1, LZMA2, LDSBITS>(jobs + g, 0, (uint8_t*)spill.data(), probs.data(), 0, nullptr);
     }
+}
+extern "C" void emu_lzma_mode(swc::Job* jobs, size_t n, int is_lzma2, int mode) {
+    static_assert(swc::lzma::kMaxLdsLitBits == 4, "mode 0 is swc_lzma_kernel<LZMA2, 4>");
+    if (mode == 1) is_lzma2 ? emu_lzma_launch<true, -1>(jobs, n) : emu_lzma_launch<false, -1>(jobs, n);
+    else is_lzma2 ? emu_lzma_launch<true, 4>(jobs, n) : emu_lzma_launch<false, 4>(jobs, n);
 }
 extern "C" void emu_lzma(swc::Job* jobs, size_t n, int is_lzma2) { emu_lzma_mode(jobs, n, is_lzma2, 0); }
 
-// BZip2: the three stages run back to back for each job, single logical lane (WAVE = 1).
-extern "C" void emu_bzip2_block(swc::Job* jobs, size_t n, size_t lcap) {
-    using namespace swc::bzip2;
-    std::vector<uint8_t> ws(ws_bytes_per_job(lcap) + 64);
-    std::vector<uint32_t> cnt(256 + 256);
-    Stage1Lds lds;
-    Stage3Lds lds3;
+// stage 3c (swc_bzip2_crc_kernel keeps its body in kernels.hip: restated here)
+static void emu_bzip2_crc(swc::Job& job) {
     static swc::crc::Lds<1, uint32_t> crc_lds;
+    if (job.status == SWC_OK) swc::bzip2::stage3_check_crc(job, swc::crc::crc_group<1, uint32_t, true>(job.out, job.out_len, &crc_lds, 0));
+}
+using BzLds = std::array<uint8_t, swc::kBzLdsBytes>;
+
+// BZip2 as launch_bzip2 issues it without the team walk: block kernel | expand | CRC, job by job in one workspace.
+extern "C" void emu_bzip2_block(swc::Job* jobs, size_t n, size_t lcap) {
+    std::vector<uint8_t> ws(swc::bzip2::ws_bytes_per_job(lcap) + 64);
     for (size_t g = 0; g < n; g++) {
-        std::memset(&lds, 0xEE, sizeof lds);
         std::fill(ws.begin(), ws.end(), (uint8_t)0xCD);
-        Workspace w = carve(ws.data(), 0, lcap);
-        stage1_job<1>(jobs[g], &lds, w, 0);
-        stage2_job(w, cnt.data());
-        std::memset(&lds3, 0xEE, sizeof lds3);
-        stage3_walk_job<1>(jobs[g], w, &lds3, 0);
-        if (stage3_expand_needed(w)) stage3_expand_job(jobs[g], w);
-        if (jobs[g].status == SWC_OK)
-            stage3_check_crc(jobs[g], swc::crc::crc_group<1, uint32_t, true>(jobs[g].out, jobs[g].out_len, &crc_lds, 0));
+        swc::jobk::bzip2_block<1, false>(jobs + g, 0, ws.data(), lcap, emu_lds<BzLds>()->data(), 0, 0);
+        swc::jobk::bzip2_expand(jobs + g, 0, ws.data(), lcap);
+        emu_bzip2_crc(jobs[g]);
     }
 }
 
@@ -206,31 +117,16 @@ extern "C" void emu_bzip2_block_team(swc::Job* all_jobs, size_t n_all, size_t lc
     using namespace swc::bzip2;
     const size_t per = ws_bytes_per_job(lcap), kAtOnce = 24;          // (the workspaces of a launch exist side by side: 24 jobs at a time)
     std::vector<uint8_t> ws(per * std::min(n_all, kAtOnce) + 64);
-    std::vector<uint32_t> cnt(256 + 256);
-    Stage1Lds lds;
-    static FinishLds fl;
-    static swc::crc::Lds<1, uint32_t> crc_lds;
     for (size_t j0 = 0; j0 < n_all; j0 += kAtOnce) {
         swc::Job* jobs = all_jobs + j0;
         const size_t n = std::min(kAtOnce, n_all - j0);
         std::fill(ws.begin(), ws.end(), (uint8_t)0xCD);
-        for (size_t g = 0; g < n; g++) {
-            std::memset(&lds, 0xEE, sizeof lds);
-            Workspace w = carve(ws.data(), g, lcap);
-            stage1_job<1>(jobs[g], &lds, w, 0);
-            stage2_job(w, cnt.data());
-        }
+        for (uint32_t g = 0; g < n; g++) swc::jobk::bzip2_block<1, false>(jobs, g, ws.data(), lcap, emu_lds<BzLds>()->data(), 0, 1);
         for (uint32_t t = 0; t < kTeams; t++) team_prep<1>(ws.data(), lcap, (uint32_t)n, t, 0);
         for (uint32_t d = 0; d < (one_thread ? 1u : kTeams); d++) team_walk(ws.data(), lcap, (uint32_t)n, ((uint32_t)start_team + d) % kTeams);
-        for (size_t g = 0; g < n; g++) {
-            Workspace w = carve(ws.data(), g, lcap);
-            std::memset(&fl, 0xEE, sizeof fl);
-            team_finish<1>(jobs[g], w, &fl, 0);
-            if (stage3_expand_needed(w)) stage3_expand_job(jobs[g], w);
-            else g_team_finished++;
-            if (jobs[g].status == SWC_OK)
-                stage3_check_crc(jobs[g], swc::crc::crc_group<1, uint32_t, true>(jobs[g].out, jobs[g].out_len, &crc_lds, 0));
-        }
+        for (uint32_t g = 0; g < n; g++) swc::jobk::bzip2_team_finish<1>(jobs, g, ws.data(), lcap, emu_lds<FinishLds>(), 0);
+        for (uint32_t g = 0; g < n; g++) if (!swc::jobk::bzip2_expand(jobs, g, ws.data(), lcap)) g_team_finished++;
+        for (uint32_t g = 0; g < n; g++) emu_bzip2_crc(jobs[g]);
     }
 }
 
@@ -249,9 +145,8 @@ extern "C" void emu_copy_records(const uint32_t* recs, uint32_t nrec, const uint
     if (copier == 3) emu_copy<swc::lzc::CfgDeflate>(j, ws.data(), wsb);
     else if (copier) emu_copy<swc::lzc::CfgLz4>(j, ws.data(), wsb);
     else {
-        alignas(16) static swc::lzr::Lds<512, 16> rl;
-        std::memset(&rl, 0xEE, sizeof rl);
-        swc::lzr::resolve_job<512, 16, 32768, true>(j, ws.data(), wsb, &rl);
+        using namespace swc;   // (FAR: `out` may sit anywhere, so every source is read back from it)
+        lzr::resolve_job<kInflateResolveThreads, kInflateRingLog2, kInflateKeep, true>(j, ws.data(), wsb, emu_lds<lzr::Lds<kInflateResolveThreads, kInflateRingLog2>>());
     }
 }
 
@@ -336,7 +231,6 @@ extern "C" size_t emu_lz4_records(const uint8_t* in, size_t in_len, uint8_t* out
 // ---- checksums: the group kernels run with T real host threads and a pthread barrier behind swc::group_sync ----------
 #include <thread>
 #include <pthread.h>
-#include "../../swcompression_amd/csrc/crc32_group.h"
 #include "../../swcompression_amd/csrc/checksum_group.h"
 
 namespace {
@@ -387,7 +281,8 @@ extern "C" uint64_t emu_checksum(int kind, const uint8_t* p, size_t n) {
     return 0;
 }
 
-// Delta filter: the group kernel with T real host threads (same barrier plumbing as the checksums)
+// Delta filter: the group kernel with T real host threads (same barrier plumbing as the checksums; swc_delta_kernel keeps its body
+// in kernels.hip)
 #include "../../swcompression_amd/csrc/delta_group.h"
 extern "C" void emu_delta(const uint8_t* in, uint8_t* out, size_t n, unsigned distance) {
     constexpr int T = 256;

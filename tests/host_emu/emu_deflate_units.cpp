@@ -1,17 +1,51 @@
-// emu_deflate_units.cpp -- TEST INFRASTRUCTURE.  A Deflate launch with joined and open units -- phase 1 with the OPEN rule
-// (csrc/inflate_sync.h), the placing scan (csrc/deflate_place.h), the copy (csrc/lz_copy.h or csrc/lz_resolve.h) -- compiled for
-// the HOST (g++ -DSWC_HOST_EMULATION): the three steps one after the other over all jobs, as kernels.hip issues them.  Part of
-// libswc_emu.so (emu.cpp includes it).  Never shipped.
+// emu_deflate_units.cpp -- TEST INFRASTRUCTURE.  A Deflate launch -- phase 1 with the OPEN rule, the placing scan
+// (csrc/deflate_place.h), the copy, the fused CRC-32 -- compiled for the HOST (g++ -DSWC_HOST_EMULATION): the kernel bodies of
+// csrc/job_kernels.h in the order launch_inflate issues the kernels.  Part of libswc_emu.so (emu.cpp includes it).  Never shipped.
 //
 // With -DEMU_DEFLATE_UNITS_MAIN the file is a stand-alone program (for -fsanitize=address,undefined): it reads runs and what is
 // expected of them from a file written by tests/test_deflate_units_emulation.py, runs every case at the sixteen alignments of its
-// buffers, in the three lane orders, with both copiers, both copy orders and the team instantiation of phase 1, and compares; the
-// placing scan runs on the size lists of the same test as well.
+// buffers, in the three lane orders, with both copiers, both copy orders, the team instantiation of phase 1 and the CRC form of the
+// copy, and compares; the placing scan runs on the size lists of the same test as well.
 #include "emu_util.h"
-#include "../../swcompression_amd/csrc/inflate_lane.h"
-#include "../../swcompression_amd/csrc/inflate_sync.h"
-#include "../../swcompression_amd/csrc/lz_copy.h"
 #include "../../swcompression_amd/csrc/deflate_place.h"
+
+// phase 1 of job g: swc_inflate_team_kernel (its helpers' rows in an allocation of their own) or swc_inflate_sync_kernel
+static void emu_inflate_phase1(swc::Job* jobs, uint32_t g, const EmuWs& ws, int team) {
+    using namespace swc;
+    if (team) {
+        std::vector<uint8_t> rows(jobk::kTeamScratchBytes + 16, (uint8_t)0xCD);
+        jobk::inflate_team<1>(jobs + g, 0, ws.from(g), rows.data(), emu_lds<std::array<inflate::SyncLds, inflate::kTeamWaves>>()->data(),
+                              emu_lds<inflate::TeamShared>(), 0, 0);
+    } else {
+        jobk::inflate_sync<1>(jobs, g, ws, emu_lds<inflate::SyncLds>(), 0, nullptr);
+    }
+}
+// phase 2 of job g.  copier: 0 = swc_lz_resolve_kernel (then, with `crcs`, swc_crc32_kernel), else swc_lz_copy_kernel or, with
+// `crcs`, swc_lz_copy_crc32_kernel (2: in the 7 KiB window).  The streams of kCrcGroupLen and more are swc_crc32_group_kernel's.
+template <typename CFG>
+static void emu_lz_copy(const swc::Job* jobs, uint32_t g, const EmuWs& ws, uint32_t* crcs) {
+    using namespace swc;
+    if (crcs) jobk::lz_copy<CFG, true>(jobs, g, ws, emu_lds<lzc::Lds<CFG::kWin>>(), 0, crcs, emu_wave_consts());
+    else jobk::lz_copy<CFG, false>(jobs, g, ws, emu_lds<lzc::Lds<CFG::kWin>>(), 0);
+}
+static void emu_inflate_phase2(const swc::Job* jobs, uint32_t g, const EmuWs& ws, int copier, uint32_t* crcs) {
+    using namespace swc;
+    if (copier == 2) return emu_lz_copy<lzc::CfgLz4>(jobs, g, ws, crcs);
+    if (copier) return emu_lz_copy<lzc::CfgDeflate>(jobs, g, ws, crcs);
+    jobk::lz_resolve(jobs, g, ws, emu_lds<lzr::Lds<kInflateResolveThreads, kInflateRingLog2>>(), nullptr);
+    if (crcs) jobk::crc32_wave(jobs, g, crcs, emu_wave_consts(), 0);
+}
+
+// Deflate, every job through both phases before the next (one workspace at a time; no joined units: the scan has nothing to place)
+extern "C" uint64_t emu_team_adopted(int reset) { const uint64_t v = swc::inflate::g_team_adopted; if (reset) swc::inflate::g_team_adopted = 0; return v; }
+extern "C" void emu_inflate_sync(swc::Job* jobs, size_t n) {
+    std::vector<uint8_t> one;
+    for (size_t g = 0; g < n; g++) {
+        emu_ws_give(one, jobs[g].out_cap);
+        emu_inflate_phase1(jobs + g, 0, EmuWs{&one, 0}, g_team);
+        emu_inflate_phase2(jobs + g, 0, EmuWs{&one, 0}, g_copier, nullptr);
+    }
+}
 
 // The placing scan alone over a job list whose out_len / out_cap / aux are given: tiles in forward (0) or reverse (1) order.
 extern "C" void emu_deflate_place(swc::Job* jobs, size_t n, int tiles_reversed) {
@@ -19,46 +53,32 @@ extern "C" void emu_deflate_place(swc::Job* jobs, size_t n, int tiles_reversed) 
     for (uint32_t i = 0; i < tiles; i++) swc::defp::place_tile(jobs, (uint32_t)n, tiles_reversed ? tiles - 1 - i : i);
 }
 
-// One launch of SWC_CODEC_DEFLATE: phase 1 | place | copy.  copier: 1 = lz_copy.h (the wave kernel), 0 = lz_resolve.h (the
-// workgroup kernel); team: phase 1 by a team of wavefronts; reversed: the tiles and the copies from the last job to the first.
-extern "C" void emu_deflate_units(swc::Job* jobs, size_t n, int copier, int team, int reversed) {
-    using namespace swc;
-    alignas(16) static inflate::SyncLds sl;
-    alignas(16) static lzr::Lds<512, 16> rl;
-    alignas(16) static lzc::Lds<lzc::CfgDeflate::kWin> cl;
-    std::vector<std::vector<uint8_t>> ws(n);
+// One launch of SWC_CODEC_DEFLATE: phase 1 | place | copy.  copier: 1 = the wave kernel, 0 = the workgroup kernel; team: phase 1 by
+// a team of wavefronts; reversed: the tiles and the copies from the last job to the first; crcs: nullptr, or n words the launch
+// leaves as launch_inflate does.
+extern "C" void emu_deflate_units(swc::Job* jobs, size_t n, int copier, int team, int reversed, uint32_t* crcs) {
+    std::vector<std::vector<uint8_t>> areas(n);
+    const EmuWs ws{areas.data(), 0};
     for (size_t g = 0; g < n; g++) {
-        const size_t wsb = lzr::ws_bytes_per_job(jobs[g].out_cap);
-        ws[g].assign(wsb + 16, (uint8_t)0xCD);
-        Job job = jobs[g];
-        if (team) {
-            EmuTeam t;
-            inflate::inflate_sync_job<true>(job, t.tm.lds, ws[g].data(), wsb, 0, 1, nullptr, &t.tm);
-        } else {
-            std::memset(&sl, 0xEE, sizeof sl);
-            inflate::inflate_sync_job(job, &sl, ws[g].data(), wsb, 0, 1);
-        }
-        put_result<true>(jobs, (uint32_t)g, job);
+        emu_ws_give(areas[g], jobs[g].out_cap);
+        emu_inflate_phase1(jobs, (uint32_t)g, ws, team);
     }
     emu_deflate_place(jobs, n, reversed);
-    for (size_t i = 0; i < n; i++) {
-        const size_t g = reversed ? n - 1 - i : i;
-        const size_t wsb = ws[g].size() - 16;
-        const Job job = jobs[g];
-        if (copier) {
-            std::memset(&cl, 0xEE, sizeof cl);
-            lzc::copy_job<lzc::CfgDeflate>(job, ws[g].data(), wsb, &cl);
-        } else {
-            std::memset(&rl, 0xEE, sizeof rl);
-            lzr::resolve_job<512, 16, 32768>(job, ws[g].data(), wsb, &rl);
-        }
-    }
+    for (size_t i = 0; i < n; i++) emu_inflate_phase2(jobs, (uint32_t)(reversed ? n - 1 - i : i), ws, copier, crcs);
 }
 
 #ifdef EMU_DEFLATE_UNITS_MAIN
 namespace {
 struct JobSpec { int32_t aux; std::vector<uint8_t> in; uint32_t cap; int32_t status; uint32_t pinned, out_len; int32_t aux_out; uint32_t consumed; std::vector<uint8_t> want; };
 struct Buf { uint8_t* raw; size_t mis, room, alloc, end; };
+uint32_t plain_crc32(const uint8_t* p, size_t n) {   // bit by bit: the reference of the CRC modes
+    uint32_t c = 0xFFFFFFFFu;
+    for (size_t i = 0; i < n; i++) {
+        c ^= p[i];
+        for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
+    }
+    return ~c;
+}
 
 // The placing scan on job lists given by their sizes (the lists of tests/test_deflate_units_emulation.py), against the serial rule.
 int check_place() {
@@ -109,9 +129,11 @@ int main(int argc, char** argv) {
             j.aux = (int32_t)r.u32(); j.in = r.bytes(r.u32()); j.cap = r.u32(); j.status = (int32_t)r.u32(); j.pinned = r.u32(); j.out_len = r.u32();
             j.aux_out = (int32_t)r.u32(); j.consumed = r.u32(); j.want = r.bytes(r.u32());
         }
-        // modes: 3 lane orders x 2 copiers x 2 copy orders with one wave per unit, and the team of wavefronts once per lane order
-        for (int mode = 0; mode < 15; mode++) {
-            const int order = mode % 3, team = mode >= 12, copier = team ? 1 : (mode / 3) & 1, reversed = team ? 0 : mode / 6;
+        // modes: 3 lane orders x 2 copiers x 2 copy orders with one wave per unit, the team of wavefronts once per lane order, and
+        // the wave copier that ends with the CRC-32 of its output once per lane order
+        for (int mode = 0; mode < 18; mode++) {
+            const int order = mode % 3, team = mode >= 12 && mode < 15, crc = mode >= 15, copier = mode >= 12 ? 1 : (mode / 3) & 1, reversed = mode >= 12 ? 0 : mode / 6;
+            std::vector<uint32_t> crcs(js.size(), 0xA5A5A5A5u);
             for (size_t mis = 0; mis < 16; mis++) {
                 if (js.size() > 64 && mis != 0 && mis != 7) continue;   // (the long lists: two alignments)
                 emu_set_order(order);
@@ -139,11 +161,11 @@ int main(int argc, char** argv) {
                     }
                     buf_of[i] = (int)bufs.size() - 1;
                 }
-                emu_deflate_units(jobs.data(), jobs.size(), copier, team, reversed);
+                emu_deflate_units(jobs.data(), jobs.size(), copier, team, reversed, crc ? crcs.data() : nullptr);
                 bool ok = true;
                 for (size_t i = 0; i < js.size(); i++) {
                     ok = ok && jobs[i].status == js[i].status && jobs[i].aux == js[i].aux_out;
-                    if (buf_of[i] < 0) { ok = ok && jobs[i].out_len == 0 && jobs[i].in_consumed == 0; continue; }   // (joined to nothing)
+                    if (buf_of[i] < 0) { ok = ok && jobs[i].out_len == 0 && jobs[i].in_consumed == 0 && (!crc || crcs[i] == 0u); continue; }   // (joined to nothing)
                     Buf& b = bufs[(size_t)buf_of[i]];
                     if (!(js[i].aux & 1)) b.end = 0;
                     ok = ok && jobs[i].out == b.raw + b.mis + b.end;                                   // right behind what its predecessor says exists
@@ -151,6 +173,7 @@ int main(int argc, char** argv) {
                     if (js[i].pinned)
                         ok = ok && jobs[i].out_len == js[i].out_len && jobs[i].in_consumed == js[i].consumed && made == js[i].want.size() && b.end + made <= b.room &&
                              (made == 0 || memcmp(b.raw + b.mis + b.end, js[i].want.data(), made) == 0);
+                    if (crc) ok = ok && crcs[i] == plain_crc32(b.raw + b.mis + b.end, made);   // (every case is far below kCrcGroupLen)
                     b.end += made;
                 }
                 for (Buf& b : bufs) {
@@ -158,7 +181,7 @@ int main(int argc, char** argv) {
                     for (size_t i = b.mis + b.end; i < b.alloc; i++) ok = ok && b.raw[i] == 0xA5;   // nothing behind what the run produced
                     free(b.raw);
                 }
-                if (!ok) { fprintf(stderr, "case %u order %d copier %d team %d reversed %d misalignment %zu: mismatch\n", c, order, copier, team, reversed, mis); bad++; }
+                if (!ok) { fprintf(stderr, "case %u order %d copier %d team %d reversed %d crc %d misalignment %zu: mismatch\n", c, order, copier, team, reversed, crc, mis); bad++; }
             }
         }
     }

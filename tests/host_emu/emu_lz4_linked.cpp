@@ -1,48 +1,43 @@
-// emu_lz4_linked.cpp -- TEST INFRASTRUCTURE.  The LZ4 path for jobs with history -- the parse with history (csrc/lz4_wave.h), the
-// copier with history (csrc/lz_copy.h) and the chain walk (csrc/lz4_chain.h) -- compiled for the HOST (g++ -DSWC_HOST_EMULATION):
-// the three steps of a launch one after the other, as kernels.hip issues them.  Part of libswc_emu.so (emu.cpp includes it).  Never
-// shipped.
+// emu_lz4_linked.cpp -- TEST INFRASTRUCTURE.  A launch of LZ4 blocks with a workspace -- the lane decoder, the parse with and without
+// history, the byte-cell resolver, the chain copy -- compiled for the HOST (g++ -DSWC_HOST_EMULATION): the kernel bodies of
+// csrc/job_kernels.h in the order launch_lz4 issues the kernels, each over all jobs.  Part of libswc_emu.so (emu.cpp includes it).
+// Never shipped.
 //
 // With -DEMU_LZ4_LINKED_MAIN the file is a stand-alone program (for -fsanitize=address,undefined): it reads chains and what the
 // oracle says about them from a file written by tests/test_lz4_linked_emulation.py, runs every chain at the sixteen alignments
-// of its buffer in the three lane orders, in allocations of exactly the size the contract asks for, and compares.
+// of its buffer in the three lane orders with both copier choices, in allocations of exactly the size the contract asks for, and
+// compares.
 #include "emu_util.h"
-#include "../../swcompression_amd/csrc/lz4_lane.h"
-#include "../../swcompression_amd/csrc/lz4_chain.h"
 
-namespace {
-struct Areas {
-    std::vector<std::vector<uint8_t>> a;
-    uint8_t* area(uint32_t g) const { return const_cast<uint8_t*>(a[g].data()); }
-    size_t bytes(uint32_t g) const { return a[g].size() - 16; }
-};
-}  // namespace
-
-// One launch of SWC_CODEC_LZ4_BLOCK with a workspace: lane decoder | parse | chain copy, each over all jobs.
-extern "C" void emu_lz4_linked(swc::Job* jobs, size_t n) {
+// copier != 0: a launch of kCopierMin jobs and more -- one record-mode parse, the chain copier over all jobs; 0: a smaller one --
+// the jobs without history through the plain parse and the byte-cell resolver, the others as above.  CFG, RM: test-only.
+template <typename CFG, int RM>
+static void emu_lz4_launch(swc::Job* jobs, uint32_t n, int copier) {
     using namespace swc;
-    alignas(16) static uint8_t stage[lz4w::kStageLds];
-    alignas(16) static lzc::Lds<lzc::CfgLz4::kWin> lds;
-    Areas ws;
-    ws.a.resize(n);
-    for (size_t g = 0; g < n; g++) ws.a[g].assign(lzr::ws_bytes_per_job(jobs[g].out_cap) + 16, (uint8_t)0xCD);
-    for (size_t g = 0; g < n; g++)
-        if (lz4w::lane_job(jobs[g])) lz4::lz4_block_job(jobs[g]);
-    for (size_t g = 0; g < n; g++) {
-        if (lz4w::lane_job(jobs[g])) continue;
-        Job job = jobs[g];
-        uint64_t hist = 0;
-        if (!lz4w::parse_preset(job, hist)) {
-            std::memset(stage, 0xEE, sizeof stage);
-            lz4w::lz4_parse_job<1, 2>(job, ws.area((uint32_t)g), ws.bytes((uint32_t)g), 0, stage, nullptr, hist);
-        }
-        put_result(jobs, (uint32_t)g, job);
+    using Stage = std::array<uint8_t, lz4w::kStageLds>;
+    std::vector<std::vector<uint8_t>> areas(n);
+    for (uint32_t g = 0; g < n; g++) emu_ws_give(areas[g], jobs[g].out_cap);
+    const EmuWs ws{areas.data(), 0};
+    for (uint32_t g = 0; g < n; g++) jobk::lz4_lane(jobs, g, 1);
+    if (copier) {
+        for (uint32_t g = 0; g < n; g++) jobk::lz4_parse<1, RM>(jobs, g, n, ws, emu_lds<Stage>()->data(), 0, nullptr, 0);
+    } else {
+        for (uint32_t g = 0; g < n; g++) jobk::lz4_parse<1, 0>(jobs, g, n, ws, emu_lds<Stage>()->data(), 0, nullptr, 2);
+        for (uint32_t g = 0; g < n; g++) jobk::lz4_parse<1, RM>(jobs, g, n, ws, emu_lds<Stage>()->data(), 0, nullptr, 1);
+        for (uint32_t g = 0; g < n; g++) jobk::lz4_resolve(jobs, g, n, ws, emu_lds<lzr::Lds<lz4w::kResolveThreads, lz4w::kRingLog2>>(), nullptr);
     }
-    for (size_t g = 0; g < n; g++) {
-        std::memset(&lds, 0xEE, sizeof lds);
-        lz4w::copy_chain<lzc::CfgLz4, 2>(jobs, (uint32_t)g, (uint32_t)n, ws, &lds);
-    }
+    for (uint32_t g = 0; g < n; g++) jobk::lz4_copy<EmuWs, CFG, RM>(jobs, g, n, ws, emu_lds<lzc::Lds<CFG::kWin>>(), copier ? 0 : 1);
 }
+
+// One launch of SWC_CODEC_LZ4_BLOCK with a workspace; copier: the launch's choice (kernels.hip: wave_copier).
+extern "C" void emu_lz4_linked(swc::Job* jobs, size_t n, int copier) {
+    using namespace swc;
+    const uint32_t m = (uint32_t)n;
+    if (g_lz4_mode == 1) g_copier == 3 ? emu_lz4_launch<lzc::CfgDeflate, 1>(jobs, m, copier) : emu_lz4_launch<lzc::CfgLz4, 1>(jobs, m, copier);
+    else g_copier == 3 ? emu_lz4_launch<lzc::CfgDeflate, 2>(jobs, m, copier) : emu_lz4_launch<lzc::CfgLz4, 2>(jobs, m, copier);
+}
+// ... with the copier choice of emu_set_copier (tests/_emu.py: lz4_block)
+extern "C" void emu_lz4_block(swc::Job* jobs, size_t n) { emu_lz4_linked(jobs, n, g_copier != 0); }
 
 #ifdef EMU_LZ4_LINKED_MAIN
 namespace {
@@ -62,7 +57,8 @@ int main(int argc, char** argv) {
         size_t room = 0;
         for (auto& j : js) { j.aux = (int32_t)r.u32(); j.in = r.bytes(r.u32()); j.cap = r.u32(); j.status = (int32_t)r.u32(); j.out_len = r.u32(); room += j.cap; }
         const std::vector<uint8_t> want = r.bytes(r.u32());
-        for (int order = 0; order < 3; order++) {
+        for (int mode = 0; mode < 6; mode++) {
+            const int order = mode % 3, copier = mode < 3;
             for (size_t mis = 0; mis < 16; mis++) {
                 emu_set_order(order);
                 // exactly the bytes the contract names: the sanitizer sees every access beyond them
@@ -83,14 +79,14 @@ int main(int argc, char** argv) {
                 }
                 jobs[0].out = raw + mis + prefix.size();
                 if (!prefix.empty()) { jobs[0].dict = raw + mis; jobs[0].dict_len = prefix.size(); }
-                emu_lz4_linked(jobs.data(), jobs.size());
+                emu_lz4_linked(jobs.data(), jobs.size(), copier);
                 bool ok = true;
                 for (size_t i = 0; i < js.size(); i++) ok = ok && jobs[i].status == js[i].status && jobs[i].out_len == js[i].out_len;
                 ok = ok && memcmp(raw + mis + prefix.size(), want.data(), want.size()) == 0;
                 for (size_t i = 0; i < mis; i++) ok = ok && raw[i] == 0xA5;
                 ok = ok && (prefix.empty() || memcmp(raw + mis, prefix.data(), prefix.size()) == 0);
                 for (size_t i = mis + prefix.size() + want.size(); i < total; i++) ok = ok && raw[i] == 0xA5;   // nothing behind what the chain produced
-                if (!ok) { fprintf(stderr, "case %u order %d misalignment %zu: mismatch\n", c, order, mis); bad++; }
+                if (!ok) { fprintf(stderr, "case %u order %d copier %d misalignment %zu: mismatch\n", c, order, copier, mis); bad++; }
                 free(raw);
             }
         }

@@ -6,8 +6,8 @@
 #include <cstring>
 #include <cstdio>
 #include <cstdlib>
-#include "../../swcompression_amd/csrc/inflate_sync.h"
-#include "../../swcompression_amd/csrc/crc32_wave.h"
+#include <array>
+#include "../../swcompression_amd/csrc/job_kernels.h"
 
 // thread order of every SIMT region (csrc/simt.h): 0 forward, 1 reverse, 2 shuffled
 extern "C" void emu_set_order(int o) { swc::simt::g_order = o; }
@@ -20,21 +20,36 @@ inline const swc::crcw::WaveConsts* emu_wave_consts() {
     return &consts;
 }
 
-// A team of wavefronts for phase 1 of one Deflate stream (inflate_sync.h) as a launch hands it over: the waves' LDS and what they
-// share filled with 0xEE, no tables held, no command; the helpers' rows 0xCD.  One at a time.
-struct EmuTeam {
-    std::vector<uint8_t> rows;
-    swc::inflate::Team tm;
-    EmuTeam() : rows((swc::inflate::kTeamWaves - 1) * swc::inflate::kTeamProvBytes + 16, (uint8_t)0xCD) {
-        alignas(16) static swc::inflate::SyncLds tl[swc::inflate::kTeamWaves];
-        alignas(16) static swc::inflate::TeamShared tsh;
-        std::memset(tl, 0xEE, sizeof tl);
-        std::memset(&tsh, 0xEE, sizeof tsh);
-        for (auto& h : tsh.hgen) h = 0;
-        tsh.cmd = 0;
-        tm.sh = &tsh; tm.lds = tl; tm.scratch = rows.data(); tm.helpers = swc::inflate::kTeamWaves - 1; tm.gen = 0;
-    }
+// ---- test-only switches: which of the product's alternatives a driver hands to the bodies of job_kernels.h ----------------------
+// phase 2: 1 = the record-granular copier of lz_copy.h as the library ships it (Deflate: 6 KiB window, LZ4: 7 KiB), 3 = the 6 KiB
+// window for both, 2 = the 7 KiB window for both, 0 = the byte-cell resolver of lz_resolve.h (a launch below kCopierMin)
+inline int g_copier = 1;
+extern "C" void emu_set_copier(int on) { g_copier = on; }
+// how the LZ4 parse tells the copier where the literals lie: 1 = eight-byte records, 2 = derived + anchors
+inline int g_lz4_mode = SWC_LZ4_RECORD_MODE;
+extern "C" void emu_set_lz4_record_mode(int m) { g_lz4_mode = m; }
+// Deflate phase 1 with a team of wavefronts per stream (launches of few streams): 0 = one wavefront
+inline int g_team = 0;
+extern "C" void emu_set_deflate_team(int on) { g_team = on; }
+
+// The workspace map of the emulation (the WS of job_kernels.h): ONE allocation per job, 0xCD-filled, of exactly the bytes the
+// contract names + 16, so that a sanitizer sees an overrun of an area.  Job g of the bodies is a[first + g].
+struct EmuWs {
+    std::vector<uint8_t>* a;
+    uint32_t first;
+    uint8_t* area(uint32_t g) const { return a[first + g].data(); }
+    size_t bytes(uint32_t g) const { return a[first + g].size() - 16; }
+    EmuWs from(uint32_t g) const { return EmuWs{a, first + g}; }
 };
+inline void emu_ws_give(std::vector<uint8_t>& area, uint64_t out_cap) { area.assign(swc::lzr::ws_bytes_per_job(out_cap) + 16, (uint8_t)0xCD); }
+
+// the LDS of a workgroup as a launch hands it over: 0xEE.  One object per type, filled again at every call.
+template <typename T>
+T* emu_lds() {
+    alignas(16) static T l;
+    std::memset(static_cast<void*>(&l), 0xEE, sizeof l);
+    return &l;
+}
 
 // the case file of a stand-alone program: read whole, then taken apart front to back; a short file ends the program
 struct Reader {

@@ -1,8 +1,10 @@
 """CPU tier of the Deflate units: phase 1 with the OPEN rule (csrc/inflate_sync.h), the placing scan (csrc/deflate_place.h) and the
 copy at any byte address (csrc/lz_copy.h, lz_resolve.h) in the host emulation, under the three lane orders, against units built
 code by code (_deflate_units_cases) and the oracle; the stand-alone program under ASan + UBSan on the same cases."""
+import ctypes as C
 import os
 import subprocess
+import zlib
 
 import pytest
 
@@ -139,10 +141,37 @@ def test_long_run_across_tiles(order, copier, rev):
     assert got[186][4] != sum(u["cap"] for u in jobs[37:186])      # not where the capacities alone would put it
 
 
+CRC_GROUP_LEN = 1 << 20   # csrc/job_kernels.h: kCrcGroupLen
+SENTINEL = 0xA5A5A5A5
+
+
+def zeros_stream(n):
+    z = zlib.compressobj(9, zlib.DEFLATED, -15)
+    return K.U(z.compress(bytes(n)) + z.flush(), n, 0)
+
+
+def test_fused_crc(expected):
+    """The copy kernel that ends with the CRC-32 of its output: after one launch over the directed runs and the long run, crcs[g] is the
+    CRC-32 of the bytes that exist at job g's `out` -- of a failed unit, of a unit over capacity, of an empty one too.  A stream of
+    kCrcGroupLen - 1 bytes gets its CRC there; one of kCrcGroupLen bytes is the group kernel's, its word keeps what it held."""
+    units = [u for run in RUNS.values() for u in run] + K.long_run() + [zeros_stream(CRC_GROUP_LEN - 1), zeros_stream(CRC_GROUP_LEN)]
+    crcs = (C.c_uint32 * len(units))(*[SENTINEL] * len(units))
+    got = E.run_units(units, misalign=5, copier=1, crcs=crcs)
+    i = 0
+    for name, run in RUNS.items():
+        check_run(name, run, expected[name], got[i:i + len(run)])
+        i += len(run)
+    for k, g in enumerate(got[:-1]):
+        assert g[5] is not None and crcs[k] == zlib.crc32(g[5]), "unit %d (status %d, out_len %d)" % (k, g[0], g[1])
+    assert [(g[0], g[1]) for g in got[-2:]] == [(K.OK, CRC_GROUP_LEN - 1), (K.OK, CRC_GROUP_LEN)]
+    assert got[-1][5] == bytes(CRC_GROUP_LEN) and crcs[len(units) - 1] == SENTINEL
+    assert any(g[0] not in (K.OK, K.CAPACITY) for g in got) and any(g[0] == K.CAPACITY for g in got) and any(g[0] == K.OK and g[1] == 0 for g in got)
+
+
 def test_standalone_program_sanitized(tmp_path, expected):
     """tests/host_emu/emu_deflate_units.cpp as a program of its own under ASan + UBSan on the same cases: every directed run (of a
     failed unit the status and aux), JOINED on job 0, residue pairs, the long run across tiles, and the place-scan lists (built into
-    the program) -- 16 alignments x 3 lane orders x both copiers x both copy orders, and the team instantiation of phase 1, in
+    the program) -- 16 alignments x 3 lane orders x both copiers x both copy orders, the team instantiation of phase 1 and the CRC form of the copy, in
     allocations of exactly the lines the contract names."""
     exe = str(tmp_path / "emu_deflate_units")
     E.compile_program(exe)

@@ -89,6 +89,43 @@ def test_orphans_are_refused():
     E.set_order(0)
 
 
+def split_launch():
+    """One job list with a job for every kernel of a launch below kCopierMin: a plain block, a block with a dictionary somewhere
+    else, one with an adjacent prefix, a chain of three linked blocks, a stored block, a block that fails."""
+    by = {c["name"]: c for c in CASES}
+    plain = corpus.lz4_block(corpus.p_text(3000, 5))
+    lane = K.orphan_behind_lane_head()
+    lane = dict(lane, name="split-dictionary-elsewhere", jobs=lane["jobs"][:1])
+    return [K.chain("split-plain", [K.J(plain, 3000)]), lane, dict(by["prefix-first-byte"]), dict(by["reach-exact-step"]),
+            K.chain("split-stored", [K.J(b"stored as it is", 15, K.STORED)]), K.chain("split-fails", [K.J(plain[:len(plain) - 7], 3000)])]
+
+
+def test_small_launch_split():
+    """A launch below kCopierMin splits its jobs over four kernels (parse without records, record-mode parse, byte-cell resolver,
+    chain copier), a larger one runs one parse and the chain copier: both against the oracle in the three lane orders, both leave the
+    same job records, the guards around every output are intact (run_chains), and the decoding paths took every job exactly once
+    between them -- all results are right, so none was skipped, and the paths' count is the number of jobs."""
+    chains = split_launch()
+    n = sum(len(ch["jobs"]) for ch in chains)
+    assert K.expected(chains[-1])[0][0] != K.OK and all(e[0] == K.OK for ch in chains[:-1] for e in K.expected(ch))
+    for order in ORDERS:
+        E.set_order(order)
+        try:
+            got = {}
+            for copier in (0, 1):
+                E.jobs_taken()
+                got[copier] = E.run_chains(chains, misalign=3, copier=copier)
+                assert E.jobs_taken() == n, "copier %d, order %d" % (copier, order)
+                for ch, res in zip(chains, got[copier]):
+                    check(ch, res)
+        finally:
+            E.set_order(0)
+        for ch, small, large in zip(chains, got[0], got[1]):
+            assert [r[:4] for r in small] == [r[:4] for r in large], ch["name"]
+            if K.expected(ch)[0][0] == K.OK:
+                assert [r[4] for r in small] == [r[4] for r in large], ch["name"]
+
+
 def test_frames_whole():
     """The liblz4 frames once more against the oracle's frame decoder: the chain's bytes are the frame's."""
     for ch in K.liblz4_cases():
