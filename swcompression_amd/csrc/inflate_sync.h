@@ -17,7 +17,8 @@
 //               aim at the row that is current, so a row is simply rewritten until it is final);
 //   chain check lane k's decode must end where lane k + 1's began; lanes for which it does not decode again (1.4 passes
 //               per round on text); when the chain holds, three wave scans give every lane its offsets and copy_prov moves
-//               the rows to their final places in the record list and the literal stream (lz_resolve.h);
+//               the rows to their final places in the record list and the literal stream (lz_resolve.h) -- these three steps
+//               are sync_round.h, shared with the LZ4 parse;
 //   fallback    anything unusual -- a symbol for the checked step, a literal run too long for one record, the capacity or the
 //               workspace inside the round, a distance beyond the output -- abandons the attempt before anything is committed;
 //               the general passes (count, scan, emit: decode_chunk) or the checked one-symbol step take over.
@@ -35,6 +36,7 @@
 
 #include "inflate_lane.h"
 #include "simt.h"
+#include "sync_round.h"
 
 namespace swc {
 namespace inflate {
@@ -520,7 +522,7 @@ struct ProvOut {
     uint32_t end, nlit, nrec, nout, flags, tail;
     int32_t need;
 };
-constexpr uint32_t kProvRow = 64u * 4u;   // bytes from one row of the scratch to the next (records and literal groups alike)
+using sround::kProvRow;
 
 template <bool NEED>
 SWC_D void decode_chunk_prov(const SyncLds* sl, const SubTab st, uint32_t start, uint32_t chunk_end, uint32_t in_bits, gptr prov,
@@ -584,53 +586,10 @@ SWC_D void decode_chunk_prov(const SyncLds* sl, const SubTab st, uint32_t start,
     r.nlit = nlit; r.nrec = (roff - rbase) / kProvRow - 1u; r.nout = nout; r.flags = flags; r.tail = tail; r.need = need;
 }
 
-// A lane's piece of the round moves from its column of the scratch to its final place: `nrec` records to `rdst` (dword
-// aligned), `nlit` literal bytes to `ldst` (any alignment).  The loads of a step read one row: coalesced.  The last,
-// incomplete literal group holds its bytes at the top.
+// A lane's piece of the round moves from its column of the scratch to its final place (sync_round.h): the last, incomplete
+// literal group of decode_chunk_prov holds its bytes at the top.
 SWC_D void copy_prov(gcptr plit, gcptr prec, uint32_t nlit, uint32_t nrec, gptr ldst, SWC_AS_GLOBAL uint32_t* rdst) {
-    // kCopyRec records and kCopyLit literal groups are loaded per step, all before the first store (the scratch of all
-    // resident waves exceeds the L2, so a load takes its several hundred cycles: one load per step would expose that latency
-    // forty times per round; a step lasts as long as the slowest lane's, so the sizes aim at ONE step for a sub-chunk of text --
-    // 23 records and 19 literals on average).  Rows past the lane's count hold something and exist (the scratch is sized for
-    // the worst case): they are loaded and not stored.
-    constexpr uint32_t kCopyRec = SWC_COPY_REC, kCopyLit = SWC_COPY_LIT;
-    const uint32_t ngrp = (nlit + 3u) >> 2;
-    for (uint32_t i = 0, g = 0; i < nrec || g < ngrp; i += kCopyRec, g += kCopyLit) {
-        uint32_t v[kCopyRec], w[kCopyLit];
-#pragma unroll
-        for (uint32_t k = 0; k < kCopyRec; k++) {
-            const uint32_t row = i + k + 1u < (uint32_t)lzr::kProvRecRows ? i + k + 1u : (uint32_t)lzr::kProvRecRows - 1u;
-            v[k] = load_u32(prec + (size_t)row * kProvRow);
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < kCopyLit; k++) {
-            const uint32_t row = g + k + 1u < (uint32_t)lzr::kProvLitRows ? g + k + 1u : (uint32_t)lzr::kProvLitRows - 1u;
-            w[k] = load_u32(plit + (size_t)row * kProvRow);
-        }
-        // (wide stores: the lanes' destinations lie apart, so the memory pipeline takes a store lane by lane -- four records or
-        // four groups per lane and instruction instead of one)
-#pragma unroll
-        for (uint32_t k = 0; k < kCopyRec; k += 4) {
-            if (i + k + 4u <= nrec) store_u128_a4((gptr)(rdst + i + k), v[k], v[k + 1], v[k + 2], v[k + 3]);
-            else {
-#pragma unroll
-                for (uint32_t q = 0; q < 4; q++) if (i + k + q < nrec) rdst[i + k + q] = v[k + q];
-            }
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < kCopyLit; k += 4) {
-            const uint32_t at = 4u * (g + k);
-            if (at + 16u <= nlit) store_u128_a4(ldst + at, w[k], w[k + 1], w[k + 2], w[k + 3]);
-            else {
-#pragma unroll
-                for (uint32_t q = 0; q < 4; q++) {
-                    const uint32_t aq = at + 4u * q;
-                    if (aq + 4u <= nlit) store_u32(ldst + aq, w[k + q]);
-                    else if (aq < nlit) { uint32_t x = w[k + q] >> (8u * (4u - (nlit - aq))); for (uint32_t z = aq; z < nlit; z++, x >>= 8) ldst[z] = (uint8_t)x; }
-                }
-            }
-        }
-    }
+    sround::copy_prov<SWC_COPY_REC, SWC_COPY_LIT, true>(plit, prec, nlit, nrec, ldst, rdst);
 }
 
 // ---- one sub-chunk, the general passes ------------------------------------------------------------------------------------
@@ -698,6 +657,88 @@ SWC_D void decode_chunk(const SyncLds* sl, const SubTab st, uint32_t start, uint
     r.end = (flags & kFlagFail) ? kPosFail : pos;
     r.nlit = nlit; r.nrec = nrec; r.nout = nout;
     r.flags = flags;
+}
+
+// ---- the steps of a round that the one-wave path and a team's helpers share (chain check, offsets, copy: sync_round.h) ------
+// Stages [B, B + kSyncStage) of the stream, zero-filled beyond the input, shifted left by two bits: LDS bit p + 2 is stream
+// bit p.  All loads of the round are issued before the first is used: ONE memory latency per round, not one per kilobyte.
+// Sets every lane's walk start: lane 0 at `first_start`, lanes 1..63 kSyncWalkBack bits IN FRONT of their sub-chunk (the further
+// a walk has come when it crosses into the sub-chunk, the surer its end is the true one, and a wrong end costs the round
+// another pass).
+template <int N>
+SWC_D void stage_round(SyncLds* sl, gcptr in, uint32_t in_len, uint32_t B, uint32_t first_start, simt::PT<uint32_t, N>& start) {
+    using simt::PT;
+    constexpr uint32_t kParts = (kSyncStage + 16u * N - 1u) / (16u * N);
+    PT<uint64_t, N> sa[kParts], sb[kParts];
+    PT<uint32_t, N> sp[kParts];
+    SIMT_BEGIN(t, N)
+#pragma unroll
+        for (uint32_t k = 0; k < kParts; k++) {
+            const uint32_t o = 16u * (uint32_t)t + k * 16u * N;
+            uint64_t a = 0, b = 0;
+            uint32_t prev = 0;
+            const uint64_t at = (uint64_t)B + o;
+            if (o < kSyncStage) {
+                if (at + 16 <= in_len) {
+                    a = load_u64(in + at); b = load_u64(in + at + 8);
+                    if (o != 0) prev = load_u32(in + at - 4);
+                } else {
+                    for (uint32_t q = 0; q < 8; q++) if (at + q < in_len) a |= (uint64_t)in[at + q] << (8 * q);
+                    for (uint32_t q = 0; q < 8; q++) if (at + 8 + q < in_len) b |= (uint64_t)in[at + 8 + q] << (8 * q);
+                    if (o != 0) for (uint32_t q = 0; q < 4; q++) if (at - 4 + q < in_len) prev |= (uint32_t)in[at - 4 + q] << (8 * q);
+                }
+            }
+            sa[k][t] = a; sb[k][t] = b; sp[k][t] = prev;
+        }
+    SIMT_END
+    SIMT_BEGIN(t, N)
+#pragma unroll
+        for (uint32_t k = 0; k < kParts; k++) {
+            const uint32_t o = 16u * (uint32_t)t + k * 16u * N;
+            if (o < kSyncStage) {
+                uint32_t* st32 = (uint32_t*)(sl->stage + o);
+                const uint64_t a = sa[k][t], b = sb[k][t];
+                const uint32_t w0 = (uint32_t)a, w1 = (uint32_t)(a >> 32), w2 = (uint32_t)b, w3 = (uint32_t)(b >> 32);
+                st32[0] = funnel32(w0, sp[k][t], 30); st32[1] = funnel32(w1, w0, 30); st32[2] = funnel32(w2, w1, 30); st32[3] = funnel32(w3, w2, 30);
+            }
+        }
+        start[t] = t == 0 ? first_start : (uint32_t)t * kSyncChunk * 8u - kSyncWalkBack;
+    SIMT_END_WAVE
+}
+// Does lane t decode (again) in this pass?  Lane 0 if it has not been decoded; any other lane if its left neighbour's end `pe`
+// is a position and not the one it was decoded from -- it then starts there.
+SWC_D bool redo_lane(int t, uint32_t& start, uint32_t pe, bool have) {
+    const bool todo = t == 0 ? !have : pe != kPosFail && (start != pe || !have);
+    if (todo && t != 0) start = pe;
+    return todo;
+}
+// My left neighbour stopped in front of my sub-chunk: at the end-of-block symbol or at something for the checked step.  Nothing
+// of mine belongs to the block (and a decode from there could run through several sub-chunks: the scratch is sized for one).
+// The lane's result (a ProvOut or a ChunkOut) is then that of a lane that failed without taking anything.
+// (Two functions: as one that tests and fills, the general pass costs swc_inflate_sync_kernel three spilled registers.)
+SWC_D bool stopped_in_front(uint32_t start, uint32_t chunk_end) { return start + kSyncChunk * 8u < chunk_end; }
+template <class R>
+SWC_D void nothing_taken(R& r) {
+    r = R{};
+    r.end = kPosFail; r.flags = kFlagFail;
+}
+// Lane t's turn of a provisional pass: if it is to decode (redo_lane), it does so once into its column of `prov` and notes what
+// came of it.  `need`: distances can still reach in front of the output (decode_chunk_prov).  Returns whether the lane decoded.
+template <int N>
+SWC_D bool prov_turn(int t, const SyncLds* sl, const SubTab st, uint32_t in_bits, gptr prov, bool need, uint32_t run0,
+                     simt::PT<uint32_t, N>& start, const simt::PT<uint32_t, N>& pe, simt::PT<bool, N>& have, simt::PT<uint32_t, N>& endp,
+                     simt::PT<uint32_t, N>& c_lit, simt::PT<uint32_t, N>& c_rec, simt::PT<uint32_t, N>& c_out, simt::PT<uint32_t, N>& flg,
+                     simt::PT<uint32_t, N>& c_tail, simt::PT<uint32_t, N>& c_need) {
+    if (!redo_lane(t, start[t], pe[t], have[t])) return false;
+    ProvOut r;
+    const uint32_t ce = ((uint32_t)t + 1u) * kSyncChunk * 8u;
+    if (stopped_in_front(start[t], ce)) nothing_taken(r);
+    else if (need) decode_chunk_prov<true>(sl, st, start[t], ce, in_bits, prov, (uint32_t)t, run0, r);
+    else decode_chunk_prov<false>(sl, st, start[t], ce, in_bits, prov, (uint32_t)t, run0, r);
+    endp[t] = r.end; c_lit[t] = r.nlit; c_rec[t] = r.nrec; c_out[t] = r.nout; flg[t] = r.flags;
+    c_tail[t] = r.tail; c_need[t] = (uint32_t)r.need;
+    have[t] = true;
+    return true;
 }
 
 // ---- a TEAM of wavefronts on one stream -----------------------------------------------------------------------------
@@ -781,46 +822,9 @@ SWC_D void team_helper_round(const Team& tm, int h) {
     }
     const uint64_t left = (uint64_t)(in_len - B) * 8;
     const uint32_t in_bits = left > 0x3FFFFFFFull ? 0x3FFFFFFFu : (uint32_t)left;
-    PT<uint32_t, N> start, endp, pe, c_lit, c_rec, c_out, flg, c_tail, c_need;
-    PT<bool, N> todo, pb, have;
-    {   // stage [B, B + kSyncStage) shifted left by two bits, zero-filled beyond the input (as sync_block does)
-        constexpr uint32_t kParts = (kSyncStage + 16u * N - 1u) / (16u * N);
-        PT<uint64_t, N> sa[kParts], sb[kParts];
-        PT<uint32_t, N> spv[kParts];
-        SIMT_BEGIN(t, N)
-#pragma unroll
-            for (uint32_t k = 0; k < kParts; k++) {
-                const uint32_t o = 16u * (uint32_t)t + k * 16u * N;
-                uint64_t a = 0, b = 0;
-                uint32_t prev = 0;
-                const uint64_t at = (uint64_t)B + o;
-                if (o < kSyncStage) {
-                    if (at + 16 <= in_len) {
-                        a = load_u64(in + at); b = load_u64(in + at + 8);
-                        if (o != 0) prev = load_u32(in + at - 4);
-                    } else {
-                        for (uint32_t q = 0; q < 8; q++) if (at + q < in_len) a |= (uint64_t)in[at + q] << (8 * q);
-                        for (uint32_t q = 0; q < 8; q++) if (at + 8 + q < in_len) b |= (uint64_t)in[at + 8 + q] << (8 * q);
-                        if (o != 0) for (uint32_t q = 0; q < 4; q++) if (at - 4 + q < in_len) prev |= (uint32_t)in[at - 4 + q] << (8 * q);
-                    }
-                }
-                sa[k][t] = a; sb[k][t] = b; spv[k][t] = prev;
-            }
-        SIMT_END
-        SIMT_BEGIN(t, N)
-#pragma unroll
-            for (uint32_t k = 0; k < kParts; k++) {
-                const uint32_t o = 16u * (uint32_t)t + k * 16u * N;
-                if (o < kSyncStage) {
-                    uint32_t* st32 = (uint32_t*)(sl->stage + o);
-                    const uint64_t a = sa[k][t], b = sb[k][t];
-                    const uint32_t w0 = (uint32_t)a, w1 = (uint32_t)(a >> 32), w2 = (uint32_t)b, w3 = (uint32_t)(b >> 32);
-                    st32[0] = funnel32(w0, spv[k][t], 30); st32[1] = funnel32(w1, w0, 30); st32[2] = funnel32(w2, w1, 30); st32[3] = funnel32(w3, w2, 30);
-                }
-            }
-            start[t] = t == 0 ? 0u : (uint32_t)t * kSyncChunk * 8u - kSyncWalkBack;
-        SIMT_END_WAVE
-    }
+    PT<uint32_t, N> start, endp, pe, c_lit, c_rec, c_out, flg, c_tail, c_need, x_lit, x_rec, x_out, xs;
+    PT<bool, N> pb, have;
+    stage_round<N>(sl, in, in_len, B, 0u, start);
     SIMT_BEGIN(t, N)
         const uint32_t ce = ((uint32_t)t + 1u) * kSyncChunk * 8u;
         endp[t] = walk_chunk(sl, st, start[t], ce, in_bits);
@@ -830,46 +834,19 @@ SWC_D void team_helper_round(const Team& tm, int h) {
     uint32_t nv = 0;
     bool ok = true, eob = false;
     for (;;) {
-        simt::wave_shift_up<N>(pe, endp, 0u);
-        SIMT_BEGIN(t, N) pb[t] = !(have[t] && (t == 0 || start[t] == pe[t])); SIMT_END
-        const uint64_t m_bad = simt::wave_ballot<N>(pb);
-        const int b = m_bad ? simt::ctz64(m_bad) : 64;
-        const uint64_t chain = b == 64 ? ~0ull : (1ull << b) - 1ull;
-        SIMT_BEGIN(t, N) pb[t] = (flg[t] & kFlagEob) != 0; SIMT_END
-        const uint64_t m_eob = simt::wave_ballot<N>(pb) & chain;
-        const int E = m_eob ? simt::ctz64(m_eob) : 64;
-        nv = (uint32_t)(E < 64 ? E + 1 : b);
+        const sround::Chain ch = sround::chain_check<N>(pe, start, endp, have, flg, 0u, kFlagEob);
+        nv = ch.nv;
         SIMT_BEGIN(t, N) pb[t] = (flg[t] & (kFlagFail | kFlagSlow)) != 0 || (t == 0 && endp[t] == kPosFail); SIMT_END
-        if (simt::wave_ballot<N>(pb) & (nv == 64 ? ~0ull : (1ull << nv) - 1ull)) { ok = false; break; }
-        if (E < 64) { eob = true; break; }
-        if (b == 64) break;
+        if (simt::wave_ballot<N>(pb) & sround::lanes_below(nv)) { ok = false; break; }
+        if (ch.E < 64) { eob = true; break; }
+        if (ch.b == 64) break;
         SIMT_BEGIN(t, N)
-            todo[t] = t != 0 && pe[t] != kPosFail && (start[t] != pe[t] || !have[t]);
-            if (todo[t]) {
-                start[t] = pe[t];
-                ProvOut r;
-                const uint32_t ce = ((uint32_t)t + 1u) * kSyncChunk * 8u;
-                if (start[t] + kSyncChunk * 8u < ce) { r.end = kPosFail; r.nlit = r.nrec = r.nout = r.tail = 0; r.flags = kFlagFail; r.need = 0; }
-                else decode_chunk_prov<true>(sl, st, start[t], ce, in_bits, prov, (uint32_t)t, 0u, r);
-                endp[t] = r.end; c_lit[t] = r.nlit; c_rec[t] = r.nrec; c_out[t] = r.nout; flg[t] = r.flags;
-                c_tail[t] = r.tail; c_need[t] = (uint32_t)r.need;
-                have[t] = true;
-            }
+            prov_turn<N>(t, sl, st, in_bits, prov, true, 0u, start, pe, have, endp, c_lit, c_rec, c_out, flg, c_tail, c_need);
         SIMT_END
     }
     // totals over the chain, and the largest shortfall of a distance against the output in front of its match INSIDE the round:
     // lane t's matches need  need[t] <= (output in front of the round) + (output of lanes 1 .. t - 1)
-    PT<uint32_t, N> x_out, xs;
-    SIMT_BEGIN(t, N)
-        const bool v = t >= 1 && (uint32_t)t < nv;
-        c_lit[t] = v ? c_lit[t] : 0u; c_rec[t] = v ? c_rec[t] : 0u; c_out[t] = v ? c_out[t] : 0u;
-        x_out[t] = c_out[t];
-        pe[t] = c_lit[t]; xs[t] = c_rec[t];
-    SIMT_END
-    simt::wave_scan_incl<N>(x_out);
-    simt::wave_scan_incl<N>(pe);
-    simt::wave_scan_incl<N>(xs);
-    const uint32_t tot_out = simt::wave_read<N>(x_out, N - 1), tot_lit = simt::wave_read<N>(pe, N - 1), tot_rec = simt::wave_read<N>(xs, N - 1);
+    const sround::Totals tot = sround::lane_offsets<N>(1u, nv, c_lit, c_rec, c_out, x_lit, x_rec, x_out);
     SIMT_BEGIN(t, N)
         const bool v = t >= 1 && (uint32_t)t < nv;
         const int32_t shortfall = (int32_t)c_need[t] - (int32_t)(x_out[t] - c_out[t]);
@@ -880,12 +857,13 @@ SWC_D void team_helper_round(const Team& tm, int h) {
     const uint32_t last = nv >= 1u ? nv - 1u : 0u;
     const uint32_t end_last = simt::wave_read<N>(endp, (int)last), tail_last = simt::wave_read<N>(c_tail, (int)last), start1 = simt::wave_read<N>(start, 1);
     SIMT_BEGIN(t, N)
-        R.c_lit[t] = c_lit[t]; R.c_rec[t] = c_rec[t];
+        const bool v = t >= 1 && (uint32_t)t < nv;
+        R.c_lit[t] = v ? c_lit[t] : 0u; R.c_rec[t] = v ? c_rec[t] : 0u;
         if (t == 0) {
             R.nv = nv; R.eob = eob ? 1u : 0u; R.ok = ok && nv >= 2u ? 1u : 0u;
             R.adopt = 0u;   // (the helper's own slot: the master writes it behind the barrier that follows, and not again before the next one)
             R.start1 = start1; R.end_last = end_last; R.tail_last = tail_last;
-            R.tot_lit = tot_lit; R.tot_rec = tot_rec; R.tot_out = tot_out; R.mneed = mneed;
+            R.tot_lit = tot.lit; R.tot_rec = tot.rec; R.tot_out = tot.out; R.mneed = mneed;
         }
     SIMT_END_WAVE
 }
@@ -988,7 +966,7 @@ SWC_D int sync_block(Lane& ln, SyncLds* sl, const SubTab st, SyncProf& pf, Team*
     gcptr in = ln.br.in;
     int result = kSyncBail;
     PT<uint32_t, N> start, endp, pe, c_lit, c_rec, c_out, flg, x_lit, x_rec, x_out, c_tail, c_need;
-    PT<bool, N> todo, pb, have;
+    PT<bool, N> pb, have;
     for (;;) {
         const uint32_t B = (uint32_t)(P >> 3) & ~3u;
         const uint32_t q0 = (uint32_t)(P - 8ull * B);
@@ -1001,48 +979,7 @@ SWC_D int sync_block(Lane& ln, SyncLds* sl, const SubTab st, SyncProf& pf, Team*
         }
         const uint64_t left = (uint64_t)(in_len - B) * 8;
         const uint32_t in_bits = left > 0x3FFFFFFFull ? 0x3FFFFFFFu : (uint32_t)left;
-        // stage [B, B + kSyncStage), zero-filled beyond the input, shifted left by two bits: LDS bit p + 2 is stream bit p.
-        // All loads of the round are issued before the first is used: ONE memory latency per round, not one per kilobyte.
-        {
-            constexpr uint32_t kParts = (kSyncStage + 16u * N - 1u) / (16u * N);
-            PT<uint64_t, N> sa[kParts], sb[kParts];
-            PT<uint32_t, N> sp[kParts];
-            SIMT_BEGIN(t, N)
-#pragma unroll
-                for (uint32_t k = 0; k < kParts; k++) {
-                    const uint32_t o = 16u * (uint32_t)t + k * 16u * N;
-                    uint64_t a = 0, b = 0;
-                    uint32_t prev = 0;
-                    const uint64_t at = (uint64_t)B + o;
-                    if (o < kSyncStage) {
-                        if (at + 16 <= in_len) {
-                            a = load_u64(in + at); b = load_u64(in + at + 8);
-                            if (o != 0) prev = load_u32(in + at - 4);
-                        } else {
-                            for (uint32_t q = 0; q < 8; q++) if (at + q < in_len) a |= (uint64_t)in[at + q] << (8 * q);
-                            for (uint32_t q = 0; q < 8; q++) if (at + 8 + q < in_len) b |= (uint64_t)in[at + 8 + q] << (8 * q);
-                            if (o != 0) for (uint32_t q = 0; q < 4; q++) if (at - 4 + q < in_len) prev |= (uint32_t)in[at - 4 + q] << (8 * q);
-                        }
-                    }
-                    sa[k][t] = a; sb[k][t] = b; sp[k][t] = prev;
-                }
-            SIMT_END
-            SIMT_BEGIN(t, N)
-#pragma unroll
-                for (uint32_t k = 0; k < kParts; k++) {
-                    const uint32_t o = 16u * (uint32_t)t + k * 16u * N;
-                    if (o < kSyncStage) {
-                        uint32_t* st32 = (uint32_t*)(sl->stage + o);
-                        const uint64_t a = sa[k][t], b = sb[k][t];
-                        const uint32_t w0 = (uint32_t)a, w1 = (uint32_t)(a >> 32), w2 = (uint32_t)b, w3 = (uint32_t)(b >> 32);
-                        st32[0] = funnel32(w0, sp[k][t], 30); st32[1] = funnel32(w1, w0, 30); st32[2] = funnel32(w2, w1, 30); st32[3] = funnel32(w3, w2, 30);
-                    }
-                }
-                // (lanes 1..63 begin their walk kSyncWalkBack bits IN FRONT of their sub-chunk: the further a walk has come when it
-                // crosses into the sub-chunk, the surer its end is the true one, and a wrong end costs the round another pass)
-                start[t] = t == 0 ? q0 : (uint32_t)t * kSyncChunk * 8u - kSyncWalkBack;
-            SIMT_END_WAVE
-        }
+        stage_round<N>(sl, in, in_len, B, q0, start);
         uint32_t nv = 0;
         bool eob = false, bail = false;
         const bool chk = (uint64_t)B + kSyncStage > in_len;   // only the last rounds of a stream can run out of input
@@ -1067,39 +1004,18 @@ SWC_D int sync_block(Lane& ln, SyncLds* sl, const SubTab st, SyncProf& pf, Team*
             bool ok = true;
             const bool need_check = pos < 32768u;   // (further in, every distance the tables can produce has its source)
             for (;;) {
-                simt::wave_shift_up<N>(pe, endp, q0);
-                SIMT_BEGIN(t, N) pb[t] = !(have[t] && (t == 0 || start[t] == pe[t])); SIMT_END
-                const uint64_t m_bad = simt::wave_ballot<N>(pb);
-                const int b = m_bad ? simt::ctz64(m_bad) : 64;
-                const uint64_t chain = b == 64 ? ~0ull : (1ull << b) - 1ull;
-                SIMT_BEGIN(t, N) pb[t] = (flg[t] & kFlagEob) != 0; SIMT_END
-                const uint64_t m_eob = simt::wave_ballot<N>(pb) & chain;
-                const int E = m_eob ? simt::ctz64(m_eob) : 64;
-                nv = (uint32_t)(E < 64 ? E + 1 : b);
+                const sround::Chain ch = sround::chain_check<N>(pe, start, endp, have, flg, q0, kFlagEob);
+                nv = ch.nv;
                 SIMT_BEGIN(t, N) pb[t] = (flg[t] & (kFlagFail | kFlagSlow)) != 0; SIMT_END
-                if (simt::wave_ballot<N>(pb) & (nv == 64 ? ~0ull : (1ull << nv) - 1ull)) { ok = false; break; }
-                if (E < 64) { eob = true; break; }
-                if (b == 64) break;
+                if (simt::wave_ballot<N>(pb) & sround::lanes_below(nv)) { ok = false; break; }
+                if (ch.E < 64) { eob = true; break; }
+                if (ch.b == 64) break;
                 SWC_SYNC_STAT(2, 1);
                 SWC_SPC(pf, 8, 1);
                 SIMT_BEGIN(t, N)
-                    todo[t] = t == 0 ? !have[t] : pe[t] != kPosFail && (start[t] != pe[t] || !have[t]);
                     SWC_SYNC_LANE_BEGIN(t_i_ == 0)
-                    if (todo[t]) {
+                    if (prov_turn<N>(t, sl, st, in_bits, ln.prov, need_check, t == 0 ? pending : 0u, start, pe, have, endp, c_lit, c_rec, c_out, flg, c_tail, c_need)) {
                         SWC_SYNC_STAT(3, 1);
-                        if (t != 0) start[t] = pe[t];
-                        ProvOut r;
-                        const uint32_t ce = ((uint32_t)t + 1u) * kSyncChunk * 8u;
-                        if (start[t] + kSyncChunk * 8u < ce) {
-                            // my left neighbour stopped in front of my sub-chunk: at the end-of-block symbol or at something for
-                            // the checked step.  Nothing of mine belongs to the block (and a decode from there could run through
-                            // several sub-chunks: the scratch is sized for one).
-                            r.end = kPosFail; r.nlit = r.nrec = r.nout = r.tail = 0; r.flags = kFlagFail; r.need = 0;
-                        } else if (need_check) decode_chunk_prov<true>(sl, st, start[t], ce, in_bits, ln.prov, (uint32_t)t, t == 0 ? pending : 0u, r);
-                        else decode_chunk_prov<false>(sl, st, start[t], ce, in_bits, ln.prov, (uint32_t)t, t == 0 ? pending : 0u, r);
-                        endp[t] = r.end; c_lit[t] = r.nlit; c_rec[t] = r.nrec; c_out[t] = r.nout; flg[t] = r.flags;
-                        c_tail[t] = r.tail; c_need[t] = (uint32_t)r.need;
-                        have[t] = true;
                     }
                     SWC_SYNC_LANE_END(t_i_ == N - 1, 1)
                 SIMT_END
@@ -1107,14 +1023,7 @@ SWC_D int sync_block(Lane& ln, SyncLds* sl, const SubTab st, SyncProf& pf, Team*
             }
             if constexpr (TEAM) if (helped) team_end(*tm);   // (the helpers' rounds are in their rows and in LDS now, whatever becomes of this one)
             if (ok) {
-                SIMT_BEGIN(t, N)
-                    const bool v = (uint32_t)t < nv;
-                    x_lit[t] = v ? c_lit[t] : 0u; x_rec[t] = v ? c_rec[t] : 0u; x_out[t] = v ? c_out[t] : 0u;
-                SIMT_END
-                simt::wave_scan_incl<N>(x_lit);
-                simt::wave_scan_incl<N>(x_rec);
-                simt::wave_scan_incl<N>(x_out);
-                const uint32_t tot_lit = simt::wave_read<N>(x_lit, N - 1), tot_rec = simt::wave_read<N>(x_rec, N - 1), tot_out = simt::wave_read<N>(x_out, N - 1);
+                const sround::Totals tot = sround::lane_offsets<N>(0u, nv, c_lit, c_rec, c_out, x_lit, x_rec, x_out);
                 SWC_SP(pf, 4)
                 if (need_check) {
                     // every distance must reach back no further than the output in front of its match (need = distance - 1 - ...)
@@ -1125,7 +1034,7 @@ SWC_D int sync_block(Lane& ln, SyncLds* sl, const SubTab st, SyncProf& pf, Team*
                     SIMT_END
                     if (simt::wave_ballot<N>(pb)) ok = false;
                 }
-                if (pos + tot_out > ln.cap || (uint64_t)nrec + tot_rec > ln.max_rec) ok = false;
+                if (pos + tot.out > ln.cap || (uint64_t)nrec + tot.rec > ln.max_rec) ok = false;
                 if (ok) {
                     SIMT_BEGIN(t, N)
                         if ((uint32_t)t < nv) {
@@ -1135,9 +1044,9 @@ SWC_D int sync_block(Lane& ln, SyncLds* sl, const SubTab st, SyncProf& pf, Team*
                     SIMT_END
                     SWC_SP(pf, 5)
                     SWC_SYNC_STAT(0, 1);
-                    pos += tot_out;
-                    nlit += tot_lit;
-                    nrec += tot_rec;
+                    pos += tot.out;
+                    nlit += tot.lit;
+                    nrec += tot.rec;
                     P = 8ull * B + simt::wave_read<N>(endp, (int)nv - 1);
                     ln.last_end = pos - (eob ? simt::wave_read<N>(c_tail, (int)nv - 1) : 0u);
                     pending = 0;
@@ -1182,32 +1091,21 @@ SWC_D int sync_block(Lane& ln, SyncLds* sl, const SubTab st, SyncProf& pf, Team*
             pending = 0;
         }
         for (;;) {
-            simt::wave_shift_up<N>(pe, endp, q0);
-            // a lane is final when it has been counted from the end of a final left neighbour
-            SIMT_BEGIN(t, N) pb[t] = !(have[t] && (t == 0 || start[t] == pe[t])); SIMT_END
-            const uint64_t m_bad = simt::wave_ballot<N>(pb);
-            const int b = m_bad ? simt::ctz64(m_bad) : 64;               // lanes [0, b) are on the true sequence
-            const uint64_t chain = b == 64 ? ~0ull : (1ull << b) - 1ull;
-            SIMT_BEGIN(t, N) pb[t] = (flg[t] & kFlagEob) != 0; SIMT_END
-            const uint64_t m_eob = simt::wave_ballot<N>(pb) & chain;
-            const int E = m_eob ? simt::ctz64(m_eob) : 64;               // the lane that met the end of the block
-            nv = (uint32_t)(E < 64 ? E + 1 : b);
+            const sround::Chain ch = sround::chain_check<N>(pe, start, endp, have, flg, q0, kFlagEob);
+            nv = ch.nv;
             SIMT_BEGIN(t, N) pb[t] = (flg[t] & kFlagFail) != 0; SIMT_END
-            const uint64_t m_fail = simt::wave_ballot<N>(pb) & (nv == 64 ? ~0ull : (1ull << nv) - 1ull);
-            if (m_fail) { bail = true; break; }                          // the true sequence holds something for the checked step
-            if (E < 64) { eob = true; break; }
-            if (b == 64) break;
+            if (simt::wave_ballot<N>(pb) & sround::lanes_below(nv)) { bail = true; break; }   // the true sequence holds something for the checked step
+            if (ch.E < 64) { eob = true; break; }                        // a lane of it met the end of the block
+            if (ch.b == 64) break;
             SWC_SYNC_STAT(2, 1);   // passes
             SWC_SPC(pf, 8, 1);
             SIMT_BEGIN(t, N)
-                todo[t] = t == 0 ? !have[t] : pe[t] != kPosFail && (start[t] != pe[t] || !have[t]);
                 SWC_SYNC_LANE_BEGIN(t_i_ == 0)
-                if (todo[t]) {
+                if (redo_lane(t, start[t], pe[t], have[t])) {
                     SWC_SYNC_STAT(3, 1);   // lane decodes
-                    if (t != 0) start[t] = pe[t];
                     ChunkOut r;
                     const uint32_t ce = ((uint32_t)t + 1u) * kSyncChunk * 8u;
-                    if (start[t] + kSyncChunk * 8u < ce) { r.end = kPosFail; r.nlit = r.nrec = r.nout = 0; r.flags = kFlagFail; }   // (see the pass above)
+                    if (stopped_in_front(start[t], ce)) nothing_taken(r);
                     else if (chk) decode_chunk<0, false, true>(sl, st, start[t], ce, in_bits, nullptr, nullptr, 0, r);
                     else decode_chunk<0, false, false>(sl, st, start[t], ce, in_bits, nullptr, nullptr, 0, r);
                     if (r.nlit > lzr::kLitRunMax) {   // a literal run may need a record of its own: count those too
@@ -1223,19 +1121,11 @@ SWC_D int sync_block(Lane& ln, SyncLds* sl, const SubTab st, SyncProf& pf, Team*
         }
         if (bail) { SWC_SYNC_STAT(1, 1); break; }
         SWC_SYNC_STAT(0, 1);   // rounds that converged
-        // exclusive offsets of the lanes [0, nv)
-        SIMT_BEGIN(t, N)
-            const bool v = (uint32_t)t < nv;
-            x_lit[t] = v ? c_lit[t] : 0u; x_rec[t] = v ? c_rec[t] : 0u; x_out[t] = v ? c_out[t] : 0u;
-        SIMT_END
-        simt::wave_scan_incl<N>(x_lit);
-        simt::wave_scan_incl<N>(x_rec);
-        simt::wave_scan_incl<N>(x_out);
-        const uint32_t tot_lit = simt::wave_read<N>(x_lit, N - 1), tot_rec = simt::wave_read<N>(x_rec, N - 1), tot_out = simt::wave_read<N>(x_out, N - 1);
+        const sround::Totals tot = sround::lane_offsets<N>(0u, nv, c_lit, c_rec, c_out, x_lit, x_rec, x_out);
         SWC_SP(pf, 4)
         const bool beyond = pos >= ln.cap;                               // size pass: nothing is kept, distances are still checked
-        if (!beyond && pos + tot_out > ln.cap) { result = kSyncBailCap; break; }
-        if (!beyond && (uint64_t)nrec + tot_rec > ln.max_rec) break;
+        if (!beyond && pos + tot.out > ln.cap) { result = kSyncBailCap; break; }
+        if (!beyond && (uint64_t)nrec + tot.rec > ln.max_rec) break;
         SIMT_BEGIN(t, N)
             SWC_SYNC_LANE_BEGIN(t_i_ == 0)
             if ((uint32_t)t < nv) {
@@ -1253,8 +1143,8 @@ SWC_D int sync_block(Lane& ln, SyncLds* sl, const SubTab st, SyncProf& pf, Team*
         SWC_SP(pf, 5)
         SIMT_BEGIN(t, N) pb[t] = (uint32_t)t < nv && (flg[t] & kFlagTrap) != 0; SIMT_END
         if (simt::wave_ballot<N>(pb)) break;                             // a distance beyond the output: the checked step reports it
-        pos += tot_out;
-        if (!beyond) { nlit += tot_lit; nrec += tot_rec; }
+        pos += tot.out;
+        if (!beyond) { nlit += tot.lit; nrec += tot.rec; }
         P = 8ull * B + simt::wave_read<N>(endp, (int)nv - 1);
         ln.last_end = pos < ln.cap ? pos : (ln.last_end > ln.cap ? ln.last_end : ln.cap);
         if (eob) { result = kSyncEob; break; }

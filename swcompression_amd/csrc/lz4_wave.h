@@ -33,6 +33,7 @@
 #include "swc_common.h"
 #include "simt.h"
 #include "lz_resolve.h"
+#include "sync_round.h"
 
 namespace swc {
 namespace lz4w {
@@ -74,8 +75,10 @@ constexpr uint32_t kPosFail = 0xFFFFFFFFu;
 enum { kLzStop = 1u, kLzFail = 2u, kLzTrap = 4u, kLzTail = 8u, kLzLong = 16u };
 #if defined(SWC_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
 #define SWC_LP(k) { const uint64_t t_ = __builtin_readcyclecounter(); pacc[k] += t_ - tlast; tlast = t_; }
+#define SWC_LPC(k, n) (pacc[k] += (n))
 #else
 #define SWC_LP(k)
+#define SWC_LPC(k, n)
 #endif
 #if defined(SWC_HOST_EMULATION)
 inline uint64_t g_lz4_stats[8];   // emulated parser: rounds, lane parses, passes, sequences taken by rounds, checked steps,
@@ -95,7 +98,9 @@ inline uint64_t g_lz4_stats[8];   // emulated parser: rounds, lane parses, passe
 // the parse and read once by the copy).  Where the rule does not hold -- the records of a sequence in long form, a literal run cut
 // into literal-only records (those continue at S, S += lit), what follows them -- the parse, which SIMULATES the copier's sum as it
 // pushes records, writes an ANCHOR (record index, S) into the area the literal stream would have had; the copier starts a new
-// group at an anchor.  An anchor stands for 128 bytes of output or more, so cap / 8 entries are room enough.
+// group at an anchor.  A sequence with more than 127 literals gets an anchor of its own AND leaves the sum one byte off (the rule
+// adds 3 for its match record without literals, the sequence spends 2 there), so the next sequence with literals gets a second:
+// at the worst two anchors per 128 + 4 + 1 + 4 bytes of output, about 68 bytes per anchor, and cap / 8 entries are room enough.
 template <int W, int RM = 0>
 struct Parser {
     static constexpr bool R8 = RM == 1, R4 = RM == 2;
@@ -432,47 +437,12 @@ struct Parser {
         if (nacc != 0u) store_u32(prov + loff, acc);   // (the bytes a full group left over in the last step)
         r.end = ip; r.nlit = nlit; r.nrec = (roff - 4u * lane) / kProvRow - 1u; r.nout = nout; r.lms = lms; r.flags = flags; r.need = need;
     }
-    // A lane's piece of the round moves from its column of the scratch to its final place: `nrec` records to `rdst` (dword
-    // aligned), `nlit` literal bytes to `ldst` (any alignment).  The loads of a step read one row: coalesced.  The last,
-    // incomplete literal group holds its bytes at the bottom.
+    // A lane's piece of the round moves from its column of the scratch to its final place (sync_round.h): the last, incomplete
+    // literal group of parse_chunk_prov holds its bytes at the bottom.
     SWC_D static void copy_prov(gcptr plit, gcptr prec, uint32_t nlit, uint32_t nrec, gptr ldst, SWC_AS_GLOBAL uint32_t* rdst) {
-        const uint32_t ngrp = (nlit + 3u) >> 2;
-        for (uint32_t i = 0, g = 0; i < nrec || g < ngrp; i += 16, g += 8) {
-            uint32_t v[16], w[8];
-#pragma unroll
-            for (uint32_t k = 0; k < 16; k++) {
-                const uint32_t row = i + k + 1u < (uint32_t)lzr::kProvRecRows ? i + k + 1u : (uint32_t)lzr::kProvRecRows - 1u;
-                v[k] = load_u32(prec + (size_t)row * kProvRow);
-            }
-#pragma unroll
-            for (uint32_t k = 0; k < 8; k++) {
-                const uint32_t row = g + k + 1u < (uint32_t)lzr::kProvLitRows ? g + k + 1u : (uint32_t)lzr::kProvLitRows - 1u;
-                w[k] = load_u32(plit + (size_t)row * kProvRow);
-            }
-#pragma unroll
-            for (uint32_t k = 0; k < 16; k += 4) {
-                if (i + k + 4u <= nrec) store_u128_a4((gptr)(rdst + i + k), v[k], v[k + 1], v[k + 2], v[k + 3]);
-                else {
-#pragma unroll
-                    for (uint32_t q = 0; q < 4; q++) if (i + k + q < nrec) rdst[i + k + q] = v[k + q];
-                }
-            }
-#pragma unroll
-            for (uint32_t k = 0; k < 8; k += 4) {
-                const uint32_t at = 4u * (g + k);
-                if (at + 16u <= nlit) store_u128_a4(ldst + at, w[k], w[k + 1], w[k + 2], w[k + 3]);
-                else {
-#pragma unroll
-                    for (uint32_t q = 0; q < 4; q++) {
-                        const uint32_t aq = at + 4u * q;
-                        if (aq + 4u <= nlit) store_u32(ldst + aq, w[k + q]);
-                        else if (aq < nlit) { uint32_t x = w[k + q]; for (uint32_t z = aq; z < nlit; z++, x >>= 8) ldst[z] = (uint8_t)x; }
-                    }
-                }
-            }
-        }
+        sround::copy_prov<16, 8, false>(plit, prec, nlit, nrec, ldst, rdst);
     }
-    static constexpr uint32_t kProvRow = 64u * 4u;
+    static constexpr uint32_t kProvRow = sround::kProvRow;
 
     // ---- R8: the same two steps without literals -- one sequence and one eight-byte record (record | literal offset << 32) per
     // step, rows of 512 bytes in the record part of the scratch (a sub-chunk holds at most (kChunk + 2) / 3 sequences)
@@ -507,22 +477,7 @@ struct Parser {
     }
     // `nrec` four-byte records from the lane's column of the scratch to `rdst` (R4)
     SWC_D static void copy_prov4(gcptr prec, uint32_t nrec, SWC_AS_GLOBAL uint32_t* rdst) {
-        for (uint32_t i = 0; i < nrec; i += 16) {
-            uint32_t v[16];
-#pragma unroll
-            for (uint32_t k = 0; k < 16; k++) {
-                const uint32_t row = i + k + 1u < (uint32_t)lzr::kProvRecRows ? i + k + 1u : (uint32_t)lzr::kProvRecRows - 1u;
-                v[k] = load_u32(prec + (size_t)row * kProvRow);
-            }
-#pragma unroll
-            for (uint32_t k = 0; k < 16; k += 4) {
-                if (i + k + 4u <= nrec) store_u128_a4((gptr)(rdst + i + k), v[k], v[k + 1], v[k + 2], v[k + 3]);
-                else {
-#pragma unroll
-                    for (uint32_t q = 0; q < 4; q++) if (i + k + q < nrec) rdst[i + k + q] = v[k + q];
-                }
-            }
-        }
+        sround::copy_prov<16, 0, false>(nullptr, prec, 0u, nrec, nullptr, rdst);
     }
     // `nrec` eight-byte records from the lane's column of the scratch to `rdst` (8-byte aligned)
     SWC_D static void copy_prov8(gcptr prec, uint32_t nrec, SWC_AS_GLOBAL uint32_t* rdst) {
@@ -599,10 +554,8 @@ struct Parser {
                 flg[t] = 0;
             SIMT_END
             SWC_LP(0)
-#if defined(SWC_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
-            pacc[5]++;
-            pacc[6]++;
-#endif
+            SWC_LPC(5, 1);
+            SWC_LPC(6, 1);
             SWC_LZ4_STAT(0, 1);
             SWC_LZ4_STAT(2, 1);
             // the walk: where does a parse from my guess end?
@@ -614,19 +567,13 @@ struct Parser {
             uint32_t nv = 0;
             int E = 64;
             for (;;) {
-                simt::wave_shift_up<N>(pe, endp, start0);
-                SIMT_BEGIN(t, N) pb[t] = !(have[t] && (t == 0 || start[t] == pe[t])); SIMT_END
-                const uint64_t m_bad = simt::wave_ballot<N>(pb);
-                const int b = m_bad ? simt::ctz64(m_bad) : 64;           // lanes [0, b) are on the true chain
-                SIMT_BEGIN(t, N) pb[t] = flg[t] != 0; SIMT_END
-                const uint64_t m_stop = simt::wave_ballot<N>(pb) & (b == 64 ? ~0ull : (1ull << b) - 1ull);
-                E = m_stop ? simt::ctz64(m_stop) : 64;                   // the lane that stopped in front of a sequence
-                nv = (uint32_t)(E < 64 ? E + 1 : b);
-                if (E < 64 || b == 64) break;
+                // (a lane stopped in front of a sequence whatever its flags say: the round ends with it)
+                const sround::Chain ch = sround::chain_check<N>(pe, start, endp, have, flg, start0, ~0u);
+                E = ch.E;
+                nv = ch.nv;
+                if (ch.E < 64 || ch.b == 64) break;
                 SWC_LZ4_STAT(2, 1);
-#if defined(SWC_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
-                pacc[6]++;
-#endif
+                SWC_LPC(6, 1);
                 SIMT_BEGIN(t, N)
                     const bool todo = t == 0 ? !have[t] : (start[t] != pe[t] || !have[t]);
                     if (todo) {
@@ -643,19 +590,11 @@ struct Parser {
                 SIMT_END
             }
             SWC_LP(3)
-            SIMT_BEGIN(t, N)
-                const bool v = (uint32_t)t < nv;
-                x_lit[t] = v ? c_lit[t] : 0u; x_rec[t] = v ? c_rec[t] : 0u; x_out[t] = v ? c_out[t] : 0u;
-            SIMT_END
-            simt::wave_scan_incl<N>(x_lit);
-            simt::wave_scan_incl<N>(x_rec);
-            simt::wave_scan_incl<N>(x_out);
-            const uint32_t tot_lit = simt::wave_read<N>(x_lit, N - 1), tot_rec = simt::wave_read<N>(x_rec, N - 1);
-            const uint32_t tot_out = simt::wave_read<N>(x_out, N - 1);
+            const sround::Totals tot = sround::lane_offsets<N>(0u, nv, c_lit, c_rec, c_out, x_lit, x_rec, x_out);
             const uint32_t stop_flags = E < 64 ? simt::wave_read<N>(flg, E) : 0u;
             SWC_LP(2)
-            if (tot_rec == 0) return;                                         // not even one sequence: the checked step
-            if (pos + tot_out > cap || (uint64_t)nrec + tot_rec > max_rec) return;   // the capacity / the workspace: the checked step counts on
+            if (tot.rec == 0) return;                                         // not even one sequence: the checked step
+            if (pos + tot.out > cap || (uint64_t)nrec + tot.rec > max_rec) return;   // the capacity / the workspace: the checked step counts on
             // :382 every offset must reach back no further than the bytes produced in front of its match
             SIMT_BEGIN(t, N)
                 const uint64_t p0 = pos + (x_out[t] - c_out[t]) + hist;
@@ -690,11 +629,11 @@ struct Parser {
             const int last = simt::top64(m_seq);
             SIMT_BEGIN(t, N) x_lit[t] = (x_out[t] - c_out[t]) + c_lms[t]; SIMT_END
             last_match_start = (int64_t)(pos + simt::wave_read<N>(x_lit, last));
-            pos += tot_out;
-            nlit += tot_lit;
-            nrec += tot_rec;
-            sequences += tot_rec;
-            SWC_LZ4_STAT(3, tot_rec);
+            pos += tot.out;
+            nlit += tot.lit;
+            nrec += tot.rec;
+            sequences += tot.rec;
+            SWC_LZ4_STAT(3, tot.rec);
             ip = B + simt::wave_read<N>(endp, (int)nv - 1);
             if (R4) s_pred = ip;
             // anything invalid / the end of the block / a sequence no round takes (a long literal run: the next round would stage
@@ -797,7 +736,7 @@ SWC_D void lz4_parse_job(Job& job, uint8_t* ws, size_t ws_bytes, int lane, uint8
         st = SWC_E_NEED_WORKSPACE;
         ps.nrec = ps.max_rec;
     }
-    if (R4 && ps.nanc > ps.max_anc) {   // (cannot happen for an area sized by swc_batch_workspace_bytes: an anchor stands for 128 bytes of output)
+    if (R4 && ps.nanc > ps.max_anc) {   // (cannot happen for an area sized by swc_batch_workspace_bytes: an anchor stands for about 68 bytes of output or more)
         st = SWC_E_NEED_WORKSPACE;
         ps.nanc = ps.max_anc;
     }

@@ -178,6 +178,19 @@ def crc32_wave(data, misalign=0):
     return got
 
 
+lib.emu_chain_check.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.c_uint32,
+                                C.c_uint32, C.POINTER(C.c_uint32)]
+lib.emu_chain_check.restype = None
+
+
+def chain_check(start, endp, have, flg, first, stop_bits):
+    """The chain check of a sub-chunk round (sync_round.h) over 64 lanes: returns (b, E, nv)."""
+    u32 = C.c_uint32 * 64
+    out = (C.c_uint32 * 3)()
+    lib.emu_chain_check(u32(*start), u32(*endp), (C.c_uint8 * 64)(*[1 if h else 0 for h in have]), u32(*flg), first, stop_bits, out)
+    return tuple(out)
+
+
 lib.emu_delta.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t, C.c_uint]
 lib.emu_delta.restype = None
 

@@ -27,6 +27,17 @@ extern "C" void emu_sync_stats(uint64_t* out, int reset) {
     for (int i = 0; i < 8; i++) { out[i] = swc::inflate::g_sync_stats[i]; if (reset) swc::inflate::g_sync_stats[i] = 0; }
 }
 
+// The chain check of a sub-chunk round on its own (sync_round.h): 64 lanes' starts, ends, `have` and flags in, out = {b, E, nv}
+extern "C" void emu_chain_check(const uint32_t* start, const uint32_t* endp, const uint8_t* have, const uint32_t* flg, uint32_t first,
+                                uint32_t stop_bits, uint32_t* out) {
+    constexpr int N = swc::kWave;
+    swc::simt::PT<uint32_t, N> s, e, f, pe;
+    swc::simt::PT<bool, N> h;
+    for (int t = 0; t < N; t++) { s[t] = start[t]; e[t] = endp[t]; f[t] = flg[t]; h[t] = have[t] != 0; pe[t] = 0xDEADBEEFu; }
+    const swc::sround::Chain c = swc::sround::chain_check<N>(pe, s, e, h, f, first, stop_bits);
+    out[0] = (uint32_t)c.b; out[1] = (uint32_t)c.E; out[2] = c.nv;
+}
+
 // LZ4 block compression (lz4_comp.h): job.in = prefix ++ block, job.dict_len = length of the prefix
 extern "C" void emu_lz4_compress(swc::Job* jobs, size_t n) {
     for (size_t g = 0; g < n; g++) swc::jobk::lz4_compress<64>(jobs, (uint32_t)g, emu_lds<std::array<uint16_t, swc::lz4c::kHashSize>>()->data(), 0);
