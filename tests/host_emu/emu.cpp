@@ -93,12 +93,14 @@ static void emu_bzip2_crc(swc::Job& job) {
 using BzLds = std::array<uint8_t, swc::kBzLdsBytes>;
 
 // BZip2 as launch_bzip2 issues it without the team walk: block kernel | expand | CRC, job by job in one workspace.
+static uint64_t g_fused_finished = 0;   // blocks whose output came from stage 3a inside the block kernel, not from the serial fallback
+extern "C" uint64_t emu_bzip2_fused_finished(int reset) { const uint64_t v = g_fused_finished; if (reset) g_fused_finished = 0; return v; }
 extern "C" void emu_bzip2_block(swc::Job* jobs, size_t n, size_t lcap) {
     std::vector<uint8_t> ws(swc::bzip2::ws_bytes_per_job(lcap) + 64);
     for (size_t g = 0; g < n; g++) {
         std::fill(ws.begin(), ws.end(), (uint8_t)0xCD);
         swc::jobk::bzip2_block<1, false>(jobs + g, 0, ws.data(), lcap, emu_lds<BzLds>()->data(), 0, 0);
-        swc::jobk::bzip2_expand(jobs + g, 0, ws.data(), lcap);
+        if (!swc::jobk::bzip2_expand(jobs + g, 0, ws.data(), lcap)) g_fused_finished++;
         emu_bzip2_crc(jobs[g]);
     }
 }
