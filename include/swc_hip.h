@@ -100,11 +100,26 @@ typedef enum swc_lz4_aux {
  *     over-capacity job still occupies min(out_len, out_cap) bytes, and the jobs behind it are placed and decoded normally.
  *     Joined jobs with no head in front of them -- job 0 and what is joined to it -- report SWC_E_INVALID_ARGUMENT with
  *     out_len = in_consumed = 0.
- * All units of all runs are parsed in one launch; between the parse and the copy one wavefront per 64 jobs places the joined ones
- * (csrc/deflate_place.h), and the copy kernels write every unit byte-exact at whatever address it got. */
+ *   SWC_DEFLATE_LINKED (valid only together with SWC_DEFLATE_JOINED, on job i > 0): the unit SHARES THE HISTORY of the units in front
+ *     of it -- what default pigz and Z_SYNC_FLUSH leave between two markers.  The job is placed exactly as a joined job is.  It
+ *     continues the CHAIN of job i - 1; the chain's head is the nearest job in front without the bit (which may itself be joined:
+ *     a caller that knows a unit stands alone starts a new chain by leaving the bit off), and nothing in front of the head is
+ *     history.  The job's history is the last min(32768, out - head's out) bytes in front of its `out`, in place.  A distance that
+ *     reaches in front of that history is SWC_E_REF_TRAP: this status replaces whatever status the parse left (a recorded reach
+ *     lies in front of whatever stopped the parse, so it is what the reference meets first), out_len, in_consumed and aux stay
+ *     as the parse left them, and no byte of the job is written.  Every job keeps its own status, as joined jobs do -- nothing
+ *     propagates down the chain: a failed or over-capacity job still occupies min(out_len, out_cap) bytes and the jobs behind it
+ *     are placed and copied against whatever lies there (the history never leaves the run's buffer).  The bit without
+ *     SWC_DEFLATE_JOINED reports SWC_E_INVALID_ARGUMENT with out_len = in_consumed = 0, and nothing in front of such a job is
+ *     history to the jobs behind it; linked jobs with no head -- job 0 and what is joined to it -- report what joined jobs with no
+ *     head report.  SWC_DEFLATE_OPEN combines with the bit freely; aux remains an OUT field for the OPEN bit only.
+ * All units of all runs are parsed in one launch -- a linked unit with a full history taken for granted, its furthest reach noted;
+ * between the parse and the copy one wavefront per 64 jobs places the joined ones (csrc/deflate_place.h), and the copy kernels write
+ * every unit byte-exact at whatever address it got, a chain of linked units by ONE wavefront, in order (csrc/deflate_chain.h). */
 typedef enum swc_deflate_aux {
     SWC_DEFLATE_JOINED = 1,
-    SWC_DEFLATE_OPEN = 2
+    SWC_DEFLATE_OPEN = 2,
+    SWC_DEFLATE_LINKED = 4
 } swc_deflate_aux;
 
 typedef struct swc_job {
@@ -305,8 +320,8 @@ int swc_unarchive_many_devices(int kind, const uint8_t* const* archives, const s
  *           Deflate stream, uncomp_len = ISIZE.  SWC_E_INVALID_ARGUMENT if a member lacks the field.
  *   kind 3  raw Deflate: the units the stream can be cut into -- a cut behind every 00 00 FF FF (the end of an empty stored block),
  *           cuts merged until every unit but the last holds at least "deflate_unit_bytes" (swc_set_tuning; 0: one unit), no cut
- *           at the very end of the buffer.  aux = the swc_deflate_aux bits of the unit's job (all but the first JOINED, all but
- *           the last OPEN).  The markers are candidates -- they occur in stored data and in codes: a caller checks the result
+ *           at the very end of the buffer.  aux = the swc_deflate_aux bits of the unit's job (all but the first JOINED -- and LINKED,
+ *           with "deflate_units_linked" = 1 -- all but the last OPEN).  The markers are candidates -- they occur in stored data and in codes: a caller checks the result
  *           as the single-shot calls do (every unit in front of some unit k SWC_OK, still OPEN, in_consumed == in_len; unit k
  *           SWC_OK with the bit cleared) and decodes the stream whole otherwise.
  *   kind 4  LZ4 frame (LZ4.swift:278-299): the blocks of the frame the buffer opens with; aux = 1 for stored blocks; flags
@@ -428,6 +443,10 @@ const char* swc_version(void);
  *                               empty stored blocks it holds into units of at least n compressed bytes that decode in parallel in
  *                               one launch (32768 is the value the tests and tools/exp_deflate_units.py use); a stream whose units do not stand alone is decoded whole afterwards
  *                               (swc_stat "deflate_unit_fallbacks"); 0 (default, until the gain is measured: DESIGN.md 4.1.1): never cut;
+ *   "deflate_units_linked" = 0 | 1   process-wide: the units "deflate_unit_bytes" cuts -- and swc_index_blocks kind 3 lists -- are
+ *                               SWC_DEFLATE_LINKED as well, all but the first: they share the history of the units in front of them, so
+ *                               streams whose units reach back (default pigz, Z_SYNC_FLUSH) decode as units instead of falling back;
+ *                               0 (default): units that stand alone, as before;
  *   "bgzf_round_members" = 1..16384   process-wide, for tests: members per round of swc_bgzf_archive (default 16384); the file is
  *                               the same bytes whatever the round size. */
 int swc_set_tuning(const char* key, int value);

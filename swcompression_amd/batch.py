@@ -29,6 +29,7 @@ class DeviceBatch:
 
     LZ4_LINKED, LZ4_STORED = 1, 2   # aux bits of an "lz4_block" job (include/swc_hip.h: swc_lz4_aux)
     DEFLATE_JOINED, DEFLATE_OPEN = 1, 2   # aux bits of a "deflate" job (swc_deflate_aux): the units of a stream cut at its flush points
+    DEFLATE_LINKED = 4                    # ... together with DEFLATE_JOINED: the unit shares the history of the units in front of it
 
     def __init__(self, codec, units, caps, aux=None, extra=None, dict_values=None, tile=1, device="cuda:0", replicate_inputs=True,
                  select=None, dicts=None, prefixes=None, guard=0):
@@ -37,7 +38,10 @@ class DeviceBatch:
         LZ4 (tile = 1): dicts[i] = a prefix dictionary staged somewhere else (bytes or None); prefixes[i] = a prefix staged directly
         in front of job i's output (an adjacent prefix: history in place).  The output ranges follow each other in job order, so
         the head of a chain of LZ4_LINKED jobs -- of a run of DEFLATE_JOINED jobs -- owns the sum of the chain's capacities; guard = that many bytes of 0xA5 in front of
-        every unlinked job's range (and its prefix) and behind the last one -- unwritten_intact() checks them."""
+        every unlinked job's range (and its prefix) and behind the last one -- unwritten_intact() checks them.
+        Deflate: aux=[...] holds the DEFLATE_* bits of every job -- DEFLATE_OPEN | (DEFLATE_JOINED on all but the head of a run) for units
+        that stand alone, DEFLATE_JOINED | DEFLATE_LINKED for a unit that may refer to the 32,768 bytes in front of it (the units of a
+        default-pigz or Z_SYNC_FLUSH stream); a job without DEFLATE_LINKED starts a new chain of shared history."""
         import torch
         self.torch = torch
         self.lib = _lib.load()

@@ -22,7 +22,7 @@ static_assert(sizeof(swc_job) == sizeof(swc::Job), "swc_job and swc::Job must ha
 static_assert(offsetof(swc_job, status) == offsetof(swc::Job, status), "layout");
 static_assert(offsetof(swc_job, dict_len) == offsetof(swc::Job, dict_len), "layout");
 static_assert(SWC_LZ4_LINKED == swc::kLz4Linked && SWC_LZ4_STORED == swc::kLz4Stored, "aux of an LZ4 block job");
-static_assert(SWC_DEFLATE_JOINED == swc::kDeflateJoined && SWC_DEFLATE_OPEN == swc::kDeflateOpen, "aux of a Deflate job");
+static_assert(SWC_DEFLATE_JOINED == swc::kDeflateJoined && SWC_DEFLATE_OPEN == swc::kDeflateOpen && SWC_DEFLATE_LINKED == swc::kDeflateLinked, "aux of a Deflate job");
 
 namespace swc {
 
@@ -508,6 +508,7 @@ int swc_set_tuning(const char* key, int value) try {
     if (!strcmp(key, "bzip2_team_walk") && value >= 0 && value <= 2) { set_bzip2_team_walk(value); return SWC_OK; }
     if (!strcmp(key, "bgzf_round_members") && value >= 1 && value <= 16384) { set_bgzf_round_members(value); return SWC_OK; }
     if (!strcmp(key, "deflate_unit_bytes") && value >= 0) { set_deflate_unit_bytes(value); return SWC_OK; }
+    if (!strcmp(key, "deflate_units_linked") && (value == 0 || value == 1)) { set_deflate_units_linked(value); return SWC_OK; }
     if (!strcmp(key, "pinned_keep_mib") && value >= 0) { g_pinned_keep = (size_t)value << 20; return SWC_OK; }
     if (!strcmp(key, "result_cache_mib") && value >= 0) { g_result_cache = (size_t)value << 20; return SWC_OK; }
     if (!strcmp(key, "pool_keep_mib") && value >= 0) {   // applies to the current device at once, to the others when they are first used

@@ -20,6 +20,7 @@ int run_deflate(std::vector<HostUnit>& streams);
 int run_deflate_one(HostUnit& u);
 int run_deflate_one_bounded(HostUnit& u, size_t bound);
 void set_deflate_unit_bytes(int v);   // "deflate_unit_bytes" (swc_set_tuning)
+void set_deflate_units_linked(int v); // "deflate_units_linked" (swc_set_tuning)
 void set_bgzf_round_members(int v);   // "bgzf_round_members" (swc_set_tuning): members per round of swc_bgzf_archive
 // many-archive batching helpers (framing_many.cpp)
 struct Lz4Plan {

@@ -49,16 +49,22 @@ int run_one_bounded(int codec, HostUnit& u, size_t bound) {
 // in front of some unit k ended open exactly at its last byte with SWC_OK and unit k met a final block with SWC_OK; by induction
 // that is what the sequential parse does.  Anything else -- a false marker, a unit that reaches back (Z_SYNC_FLUSH), any error -- and
 // the stream is decoded whole, as ever, and THAT result is reported.
+// "deflate_units_linked" = 1: every unit but the first is SWC_DEFLATE_LINKED as well -- it shares the history of the units in front of
+// it, which one wave copies as a chain (deflate_chain.h) -- so a unit that reaches back is no reason to fall back any more: default
+// pigz and Z_SYNC_FLUSH streams decode as units.  The verdict is the same rule; a false marker or a broken stream still falls back.
 // "deflate_unit_bytes": the least compressed size of a unit, 0 = never cut.  The default is 0 -- the host paths decode as they always
 // did -- until tools/exp_deflate_units.py has shown on the device what cutting gains; callers opt in with the knob.
 static std::atomic<size_t> g_deflate_unit_bytes{0};
 void set_deflate_unit_bytes(int v) { g_deflate_unit_bytes = (size_t)v; }
 size_t deflate_unit_bytes() { return g_deflate_unit_bytes.load(); }
+static std::atomic<int> g_deflate_units_linked{0};
+void set_deflate_units_linked(int v) { g_deflate_units_linked = v; }
 
 // The units of one raw stream (swc_index_blocks kind 3): a cut behind every marker, cuts merged until every unit but the last
 // holds at least unit_bytes, no cut at the very end.  Always at least one unit; aux = the bits of its job.
 void deflate_unit_index(const uint8_t* in, size_t len, size_t unit_bytes, std::vector<BlockRef64>& out) {
     size_t start = 0;
+    const uint32_t behind = SWC_DEFLATE_JOINED | (g_deflate_units_linked.load() ? SWC_DEFLATE_LINKED : 0);   // every unit but the first
     if (unit_bytes != 0 && len >= 4) {
         const uint8_t* p = in + 2;   // (the first 0xFF of a marker is at offset 2 or later)
         const uint8_t* const end = in + len;
@@ -68,14 +74,14 @@ void deflate_unit_index(const uint8_t* in, size_t len, size_t unit_bytes, std::v
             if (p[1] == 0xFF && p[-1] == 0 && p[-2] == 0) {
                 const size_t cut = (size_t)(p - in) + 2;
                 if (cut < len && cut - start >= unit_bytes) {
-                    out.push_back({start, cut - start, 0, (uint32_t)(SWC_DEFLATE_OPEN | (out.empty() ? 0 : SWC_DEFLATE_JOINED))});
+                    out.push_back({start, cut - start, 0, (uint32_t)(SWC_DEFLATE_OPEN | (out.empty() ? 0u : behind))});
                     start = cut;
                 }
                 p += 2;
             } else p++;
         }
     }
-    out.push_back({start, len - start, 0, (uint32_t)(out.empty() ? 0 : SWC_DEFLATE_JOINED)});
+    out.push_back({start, len - start, 0, out.empty() ? 0u : behind});
 }
 
 int run_deflate(std::vector<HostUnit>& streams) {

@@ -108,6 +108,9 @@ struct Lane {
     gptr prov = nullptr;           // scratch of the wave-parallel rounds (lzr::kProvBytes), or none
     int wlane = 0;                 // this lane's number in the wave (the uniform parts run on every lane)
     int wlanes = kWave;            // lanes that share the work of the parallel parts (1 in the host emulation)
+    // SWC_DEFLATE_LINKED (include/swc_hip.h): `back` bytes of history are taken to lie in front of the unit (32,768 or none), and
+    // `reach` is the furthest a distance went in front of the unit's first byte -- the copy checks it against the history that came to be
+    uint32_t back = 0, reach = 0;
 
     SWC_HD void push(uint32_t v) {
         if (nrec < max_rec) recs[nrec] = v;

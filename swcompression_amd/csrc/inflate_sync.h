@@ -288,8 +288,12 @@ SWC_D int careful_step(Lane& ln, const Spill sp) {
         if (br.bc < e) return SWC_E_DEFLATE_SYMBOL_NOT_FOUND;  // :208
         distance = 1 + ((2 + ((uint32_t)dc & 1)) << e) + br.bits(e);  // Constants.distanceBase
     }
-    // :216-221 out[count - distance] with distance > count is a Swift trap (App. A6)
-    if ((uint64_t)distance > ln.pos) return SWC_E_REF_TRAP;
+    // :216-221 out[count - distance] with distance > count is a Swift trap (App. A6); a linked unit: beyond the history it may have
+    if ((uint64_t)distance > ln.pos) {
+        const uint32_t over = distance - (uint32_t)ln.pos;
+        if (over > ln.back) return SWC_E_REF_TRAP;
+        if (over > ln.reach) ln.reach = over;
+    }
     ln.emit_match(length, distance);
     return SWC_OK;
 }
@@ -597,20 +601,23 @@ struct ChunkOut {
     uint32_t end;     // bit position (relative to the round base) just past the last symbol taken; kPosFail: no valid decode
     uint32_t nlit, nrec, nout;
     uint32_t flags;
+    uint32_t over;    // MODE != 0, a linked unit: the furthest a distance went in front of the unit's first byte
 };
 // MODE 0: count.  MODE 1: emit literals and records.  MODE 2: check distances only (output beyond the capacity).
 // BIG: literal runs of more than lzr::kLitRunMax bytes in front of a match get a record of their own (only possible in a
 // sub-chunk that holds more than that many literals: the caller picks).  CHK: symbols may run past the end of the input.
 // Decodes from bit `start` until a lit/len symbol would begin at or beyond `chunk_end`, or the end-of-block symbol.
+// `back`: the history a linked unit may have in front of its first byte.
 // (Rounds the provisional decode abandoned, and lanes behind an early end of block: not the hot path.)
 template <int MODE, bool BIG, bool CHK>
 SWC_D void decode_chunk(const SyncLds* sl, const SubTab st, uint32_t start, uint32_t chunk_end, uint32_t in_bits, gptr lit_dst,
-                        SWC_AS_GLOBAL uint32_t* rec_dst, uint64_t out_pos0, ChunkOut& r) {
+                        SWC_AS_GLOBAL uint32_t* rec_dst, uint64_t out_pos0, ChunkOut& r, uint32_t back = 0) {
     uint32_t pos = start;
     bool dist_next = false;
-    uint32_t plen = 0, run = 0, nlit = 0, nrec = 0, nout = 0, flags = 0;
+    uint32_t plen = 0, run = 0, nlit = 0, nrec = 0, nout = 0, flags = 0, over = 0;
     uint32_t lb = 0, lbn = 0;                              // literals on their way to the literal stream, four per store
-    const uint32_t room = out_pos0 > 0x40000000ull ? 0x40000000u : (uint32_t)out_pos0;   // output in front of the sub-chunk, as far as a distance can reach
+    const uint32_t own = out_pos0 > 0x40000000ull ? 0x40000000u : (uint32_t)out_pos0;   // output in front of the sub-chunk, as far as a distance can reach
+    const uint32_t room = own + back;
     for (;;) {
         if (!dist_next && pos >= chunk_end) break;
         SWC_SYNC_STAT(4 + MODE, 1);
@@ -627,7 +634,10 @@ SWC_D void decode_chunk(const SyncLds* sl, const SubTab st, uint32_t start, uint
         const bool was_dist = dist_next;
         const uint32_t is_lit = (e >> 13) & 1u;
         const uint32_t val = (bfe32(bits4, 0, e) >> ((e >> 5) & 31u)) + bfe32(e, kEntBaseShift, 15) + (was_dist ? 1u : 0u);   // literal, length or distance
-        if (MODE != 0 && was_dist && val > room + nout) { flags |= kFlagTrap; break; }
+        if (MODE != 0 && was_dist && val > own + nout) {
+            if (val > room + nout) { flags |= kFlagTrap; break; }
+            if (val - (own + nout) > over) over = val - (own + nout);
+        }
         const bool big = BIG && was_dist && run > lzr::kLitRunMax;
         if (MODE == 1) {
             if (is_lit) {
@@ -657,6 +667,7 @@ SWC_D void decode_chunk(const SyncLds* sl, const SubTab st, uint32_t start, uint
     r.end = (flags & kFlagFail) ? kPosFail : pos;
     r.nlit = nlit; r.nrec = nrec; r.nout = nout;
     r.flags = flags;
+    r.over = over;
 }
 
 // ---- the steps of a round that the one-wave path and a team's helpers share (chain check, offsets, copy: sync_round.h) ------
@@ -943,6 +954,19 @@ SWC_D void team_helper_loop(const Team& tm, int h) {
 #endif
 }
 
+// A linked unit's round that passed the distance check: the furthest one of its distances goes in front of the unit's first byte
+// (lane t's matches: need[t] + 1 - the output in front of its sub-chunk), 0 if none does.
+template <int N>
+SWC_D uint32_t lanes_reach(uint64_t pos, uint32_t nv, const simt::PT<uint32_t, N>& c_need, const simt::PT<uint32_t, N>& c_out, const simt::PT<uint32_t, N>& x_out) {
+    simt::PT<uint32_t, N> xr;
+    SIMT_BEGIN(t, N)
+        const int64_t over = (int64_t)(int32_t)c_need[t] + 1 - (int64_t)(pos + (x_out[t] - c_out[t]));
+        xr[t] = (uint32_t)t < nv && over > 0 ? (uint32_t)over : 0u;
+    SIMT_END
+    simt::wave_scan_max_incl<N>(xr);
+    return simt::wave_read<N>(xr, N - 1);
+}
+
 // ---- the rounds of one block ---------------------------------------------------------------------------------------
 // Decodes from the reader's position until the end-of-block symbol (kSyncEob) or until something the fast path leaves
 // to the checked step (kSyncBail; kSyncBailCap: the capacity lies inside the next round).  Commits whole rounds only.
@@ -964,6 +988,7 @@ SWC_D int sync_block(Lane& ln, SyncLds* sl, const SubTab st, SyncProf& pf, Team*
     uint32_t nrec = simt::uniform(ln.nrec);
     const uint32_t in_len = ln.br.len;
     gcptr in = ln.br.in;
+    const uint32_t back = simt::uniform(ln.back);   // (a linked unit: every bound of a distance by the unit's own output takes this much more)
     int result = kSyncBail;
     PT<uint32_t, N> start, endp, pe, c_lit, c_rec, c_out, flg, x_lit, x_rec, x_out, c_tail, c_need;
     PT<bool, N> pb, have;
@@ -1025,17 +1050,20 @@ SWC_D int sync_block(Lane& ln, SyncLds* sl, const SubTab st, SyncProf& pf, Team*
             if (ok) {
                 const sround::Totals tot = sround::lane_offsets<N>(0u, nv, c_lit, c_rec, c_out, x_lit, x_rec, x_out);
                 SWC_SP(pf, 4)
+                uint32_t round_reach = 0;
                 if (need_check) {
                     // every distance must reach back no further than the output in front of its match (need = distance - 1 - ...)
                     SIMT_BEGIN(t, N)
                         const uint64_t p0 = pos + (x_out[t] - c_out[t]);
                         const int32_t room = p0 > 0x40000000ull ? 0x40000000 : (int32_t)p0;
-                        pb[t] = (uint32_t)t < nv && (int32_t)c_need[t] >= room;
+                        pb[t] = (uint32_t)t < nv && (int32_t)c_need[t] >= room + (int32_t)back;
                     SIMT_END
                     if (simt::wave_ballot<N>(pb)) ok = false;
+                    if (ok && back != 0u) round_reach = lanes_reach<N>(pos, nv, c_need, c_out, x_out);
                 }
                 if (pos + tot.out > ln.cap || (uint64_t)nrec + tot.rec > ln.max_rec) ok = false;
                 if (ok) {
+                    if (round_reach > ln.reach) ln.reach = round_reach;
                     SIMT_BEGIN(t, N)
                         if ((uint32_t)t < nv) {
                             copy_prov(ln.prov + lzr::kProvRecBytes + 4u * (uint32_t)t, ln.prov + 4u * (uint32_t)t, c_lit[t], c_rec[t],
@@ -1062,8 +1090,14 @@ SWC_D int sync_block(Lane& ln, SyncLds* sl, const SubTab st, SyncProf& pf, Team*
                             const bool heob = simt::uniform(R.eob) != 0u;
                             if (!heob && hnv != (uint32_t)N) break;
                             const uint32_t hl = simt::uniform(R.tot_lit), hr = simt::uniform(R.tot_rec), ho = simt::uniform(R.tot_out);
-                            if (pos < 32768u && (int64_t)(int32_t)(simt::uniform(R.mneed) - 0x80000000u) >= (int64_t)pos) break;   // a distance beyond the output
+                            uint32_t hreach = 0;
+                            if (pos < 32768u) {
+                                const int64_t short_by = (int64_t)(int32_t)(simt::uniform(R.mneed) - 0x80000000u) + 1 - (int64_t)pos;   // the furthest a distance goes in front of the unit
+                                if (short_by > (int64_t)back) break;   // a distance beyond the output (a linked unit: beyond the history it may have)
+                                if (short_by > 0) hreach = (uint32_t)short_by;
+                            }
                             if (pos + ho > ln.cap || (uint64_t)nrec + hr > ln.max_rec) break;
+                            if (hreach > ln.reach) ln.reach = hreach;
                             SIMT_BEGIN(t, N) if (t == 0) { R.adopt = 1u; R.nlit_base = nlit; R.nrec_base = nrec; } SIMT_END
                             SWC_TEAM_STAT();       // rounds adopted
                             pos += ho;
@@ -1133,16 +1167,23 @@ SWC_D int sync_block(Lane& ln, SyncLds* sl, const SubTab st, SyncProf& pf, Team*
                 const uint32_t ce = ((uint32_t)t + 1u) * kSyncChunk * 8u;
                 const uint64_t p0 = pos + (x_out[t] - c_out[t]);
                 const bool bigs = c_lit[t] > lzr::kLitRunMax;
-                if (beyond) decode_chunk<2, false, true>(sl, st, start[t], ce, in_bits, nullptr, nullptr, p0, r);
-                else if (bigs || chk) decode_chunk<1, true, true>(sl, st, start[t], ce, in_bits, ln.lits + nlit + (x_lit[t] - c_lit[t]), ln.recs + nrec + (x_rec[t] - c_rec[t]), p0, r);
-                else decode_chunk<1, false, false>(sl, st, start[t], ce, in_bits, ln.lits + nlit + (x_lit[t] - c_lit[t]), ln.recs + nrec + (x_rec[t] - c_rec[t]), p0, r);
+                if (beyond) decode_chunk<2, false, true>(sl, st, start[t], ce, in_bits, nullptr, nullptr, p0, r, back);
+                else if (bigs || chk) decode_chunk<1, true, true>(sl, st, start[t], ce, in_bits, ln.lits + nlit + (x_lit[t] - c_lit[t]), ln.recs + nrec + (x_rec[t] - c_rec[t]), p0, r, back);
+                else decode_chunk<1, false, false>(sl, st, start[t], ce, in_bits, ln.lits + nlit + (x_lit[t] - c_lit[t]), ln.recs + nrec + (x_rec[t] - c_rec[t]), p0, r, back);
                 flg[t] = r.flags;
+                c_need[t] = r.over;   // (the provisional decode's column: free in the general passes)
             }
             SWC_SYNC_LANE_END(t_i_ == N - 1, 2)
         SIMT_END
         SWC_SP(pf, 5)
         SIMT_BEGIN(t, N) pb[t] = (uint32_t)t < nv && (flg[t] & kFlagTrap) != 0; SIMT_END
         if (simt::wave_ballot<N>(pb)) break;                             // a distance beyond the output: the checked step reports it
+        if (back != 0u && pos < 32768u) {                                // a linked unit: what the round reached for in front of the unit
+            SIMT_BEGIN(t, N) c_need[t] = (uint32_t)t < nv ? c_need[t] : 0u; SIMT_END
+            simt::wave_scan_max_incl<N>(c_need);
+            const uint32_t rr = simt::wave_read<N>(c_need, N - 1);
+            if (rr > ln.reach) ln.reach = rr;
+        }
         pos += tot.out;
         if (!beyond) { nlit += tot.lit; nrec += tot.rec; }
         P = 8ull * B + simt::wave_read<N>(endp, (int)nv - 1);
@@ -1389,7 +1430,15 @@ SWC_D void inflate_sync_job(Job& job, SyncLds* sl, uint8_t* ws, size_t ws_bytes,
     // SWC_DEFLATE_OPEN (include/swc_hip.h): the unit of a stream cut at its flush points may end where a block header would start
     const bool open = (job.aux & kDeflateOpen) != 0;
     bool ended_open = false;
-    if (lo == 0 || ln.prov == nullptr) {
+    // SWC_DEFLATE_LINKED: the unit shares the history of the joined units in front of it.  Nothing here reads output, so the parse takes
+    // a full history of 32,768 bytes for granted and notes the furthest reach in front of the unit in the stream header (pad0): the
+    // copy, which knows what history came to be, has the last word (deflate_chain.h)
+    const bool linked = (job.aux & kDeflateLinked) != 0;
+    ln.back = linked ? 32768u : 0u;
+    if (linked && (job.aux & kDeflateJoined) == 0) {
+        st = SWC_E_INVALID_ARGUMENT;   // (a unit with history stands behind its predecessor)
+        ln.br.init((gcptr)job.in, 0, 0);
+    } else if (lo == 0 || ln.prov == nullptr) {
         st = SWC_E_NEED_WORKSPACE;   // (an area smaller than swc_batch_workspace_bytes asks for)
         ln.br.init((gcptr)job.in, 0, 0);
     } else if (job.in_len > 0xFFFFFFF0ull) {
@@ -1445,7 +1494,7 @@ SWC_D void inflate_sync_job(Job& job, SyncLds* sl, uint8_t* ws, size_t ws_bytes,
     if (ws && ws_bytes >= sizeof(lzr::StreamHeader) && (lane == 0)) {
         SWC_AS_GLOBAL lzr::StreamHeader* h = (SWC_AS_GLOBAL lzr::StreamHeader*)ws;
         h->nrec = ln.nrec;
-        h->pad0 = 0;
+        h->pad0 = ln.reach;   // (0 for every job that is not linked)
         h->nlit = ln.nlit;
     }
 #if defined(SWC_PROFILE) && defined(__HIP_DEVICE_COMPILE__)

@@ -16,6 +16,7 @@
 #include "inflate_sync.h"
 #include "lz_resolve.h"
 #include "lz_copy.h"
+#include "deflate_chain.h"
 #include "lz4_lane.h"
 #include "lz4_wave.h"
 #include "lz4_chain.h"
@@ -127,6 +128,12 @@ SWC_D void lz_resolve(const Job* __restrict__ jobs, uint32_t g, const WS& wm, lz
     Job job = jobs[g];
     lzr::resolve_job<kInflateResolveThreads, kInflateRingLog2, kInflateKeep>(job, wm.area(g), wm.bytes(g), lds, prof_of(prof, g, 1));
 }
+// ... as a launch below the wave copier's threshold runs it: the chains with a linked member are the wave copier's, behind this kernel
+template <typename WS>
+SWC_D void lz_resolve_unlinked(const Job* __restrict__ jobs, uint32_t g, uint32_t n, const WS& wm, lzr::Lds<kInflateResolveThreads, kInflateRingLog2>* lds, uint64_t* prof) {
+    if (defch::chain_job(jobs, g, n)) return;
+    lz_resolve(jobs, g, wm, lds, prof);
+}
 
 // swc_lz_copy_kernel and, CRC, swc_lz_copy_crc32_kernel: phase 2 by a wavefront.  CRC: when copy_job has returned -- on whichever
 // path: no literal stream, no records, a failed stream -- the window is dead, and the wave ends with the CRC-32 of its own output
@@ -148,6 +155,56 @@ SWC_D void lz_copy(const Job* __restrict__ jobs, uint32_t g, const WS& wm, lzc::
         simt::vmem_fence();   // every store of this wave has arrived (what drain() waits for)
         const uint32_t c = crct::crc32_tail((gcptr)job.out, simt::uniform((uint32_t)len), (crct::TailConsts*)lds->win, consts);
         if (lane == 0) crcs[g] = c;
+    }
+}
+
+// ... as swc_lz_copy_kernel and swc_lz_copy_crc32_kernel run it: the chains with a linked member are swc_deflate_chain_kernel's
+template <typename CFG, bool CRC, typename WS>
+SWC_D void lz_copy_unlinked(const Job* __restrict__ jobs, uint32_t g, uint32_t n, const WS& wm, lzc::Lds<CFG::kWin>* lds, int lane, uint32_t* __restrict__ crcs = nullptr,
+                            const crcw::WaveConsts* consts = nullptr) {
+    if (defch::chain_job(jobs, g, n)) return;
+    lz_copy<CFG, CRC>(jobs, g, wm, lds, lane, crcs, consts);
+}
+
+// The chain copy of swc_deflate_chain_kernel and, CRC, swc_deflate_chain_crc32_kernel, behind the copy kernels of every Deflate launch
+// (deflate_chains below finds the heads): the wave of a job takes the linked jobs behind it along, one after the other (deflate_chain.h: SWC_DEFLATE_LINKED); it writes the status of those that
+// reached beyond their history, so the job list is not read-only here.  A job without a chain is copied as lz_copy copies it.
+// CRC: crcs[j] for every job the wave carried -- the window is dead between two jobs of a chain just as it is at the end.
+// only_chain: the launch's other jobs are another kernel's -- swc_lz_copy_kernel's or swc_lz_resolve_kernel's -- as in every launch.
+template <typename CFG, bool CRC, typename WS>
+SWC_D void deflate_copy(Job* jobs, uint32_t g, uint32_t n, const WS& wm, lzc::Lds<CFG::kWin>* lds, int lane, int only_chain, uint32_t* __restrict__ crcs = nullptr,
+                        const crcw::WaveConsts* consts = nullptr) {
+    if (only_chain && !defch::chain_job(jobs, g, n)) return;
+    defch::copy_chain(jobs, g, n, wm, [&](const Job& job, uint32_t j, uint32_t hist, bool copy) {
+        if (copy && job.dict == nullptr) lzc::copy_job<CFG, 0, true>(job, wm.area(j), wm.bytes(j), lds, hist);
+        if constexpr (CRC) {
+            static_assert(sizeof(crct::TailConsts) <= CFG::kWin, "the constants of the tail go where the window was");
+            const uint64_t len = made_bytes(job.out_len, job.out_cap);
+            if (len >= kCrcGroupLen) return;   // (swc_crc32_group_kernel's, behind this kernel)
+            simt::vmem_fence();   // every store of this wave has arrived (what drain() waits for)
+            const uint32_t c = crct::crc32_tail((gcptr)job.out, simt::uniform((uint32_t)len), (crct::TailConsts*)lds->win, consts);
+            if (lane == 0) crcs[j] = c;
+        }
+    });
+}
+
+// What a wave of swc_deflate_chain_kernel does: it looks at the tiles of 64 consecutive jobs tile, tile + step, ... -- one load of `aux`
+// per lane and one of its right neighbour's -- and copies every chain that begins there, one after the other.  A launch without a
+// linked job (every launch of section 5) costs a few hundred waves a ballot each, not a wave per job.
+template <typename CFG, bool CRC, typename WS>
+SWC_D void deflate_chains(Job* jobs, uint32_t tile, uint32_t step, uint32_t n, const WS& wm, lzc::Lds<CFG::kWin>* lds, int lane, uint32_t* __restrict__ crcs = nullptr,
+                          const crcw::WaveConsts* consts = nullptr) {
+    constexpr int N = 64;
+    for (uint64_t g0 = (uint64_t)tile * N; g0 < n; g0 += (uint64_t)step * N) {
+        simt::PT<bool, N> head;
+        SIMT_BEGIN(t, N)
+            const uint32_t g = (uint32_t)g0 + (uint32_t)t;
+            const bool linked = g < n && (jobs[g].aux & kDeflateLinked) != 0;
+            const bool next = g + 1u < n && (jobs[g + 1u].aux & kDeflateLinked) != 0;
+            head[t] = g < n && (linked ? g == 0u : next);   // (a linked job 0 has no head: its wave carries what there is of it)
+        SIMT_END
+        for (uint64_t m = simt::wave_ballot<N>(head); m; m &= m - 1u)
+            deflate_copy<CFG, CRC>(jobs, (uint32_t)g0 + (uint32_t)simt::ctz64(m), n, wm, lds, lane, 0, crcs, consts);
     }
 }
 

@@ -149,7 +149,7 @@ __global__ __launch_bounds__(kInflateResolveThreads) void swc_lz_resolve_kernel(
     __shared__ __attribute__((aligned(16))) lzr::Lds<kInflateResolveThreads, kInflateRingLog2> lzr_lds;  // static: > 64 KiB needs no opt-in this way
     uint32_t g = job_of(order, blockIdx.x, n);
     if (g >= n) return;
-    jobk::lz_resolve(jobs, g, wm, &lzr_lds, prof);
+    jobk::lz_resolve_unlinked(jobs, g, n, wm, &lzr_lds, prof);   // (the chains of linked units: the wave copier's, behind this kernel)
 }
 
 // Phase 2, record-granular (lz_copy.h): one stream per WAVEFRONT, the last few KiB of its output in an LDS window, older
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZC_WAVE
     __shared__ __attribute__((aligned(16))) lzc::Lds<lzc::CfgDeflate::kWin> lds;
     uint32_t g = job_of(order, blockIdx.x, n);
     if (g >= n) return;
-    jobk::lz_copy<lzc::CfgDeflate, false>(jobs, g, wm, &lds, (int)threadIdx.x);
+    jobk::lz_copy_unlinked<lzc::CfgDeflate, false>(jobs, g, n, wm, &lds, (int)threadIdx.x);
 }
 // LZ4: the wave of a job takes the linked jobs behind it along, one after the other (lz4_chain.h); it writes their `out` and their
 // results, so the job list is not read-only here.  only_chain: the launch's other jobs are swc_lz4_resolve_kernel's.
@@ -191,8 +191,27 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_LZC_WAVE
     __shared__ __attribute__((aligned(16))) lzc::Lds<lzc::CfgDeflate::kWin> lds;
     uint32_t g = job_of(order, blockIdx.x, n);
     if (g >= n) return;
-    jobk::lz_copy<lzc::CfgDeflate, true>(jobs, g, wm, &lds, (int)threadIdx.x, crcs, &g_crc_consts);
+    jobk::lz_copy_unlinked<lzc::CfgDeflate, true>(jobs, g, n, wm, &lds, (int)threadIdx.x, crcs, &g_crc_consts);
 }
+// The chains of linked units (deflate_chain.h), behind the copy kernels of every Deflate launch: a wave looks through tiles of 64 jobs
+// for the heads of chains (two loads of `aux` per lane, a ballot) and copies every chain it finds, job after job -- at most
+// kChainGrid waves, so that a launch of 100,000 streams without a chain pays for 1,563 waves that end at once, not for 100,000.
+// Kernels of their own: inside the copy kernels the walk's state
+// -- the job list, the workspace map, the place in the chain -- stays live across the copier and costs swc_lz_copy_crc32_kernel 96
+// bytes of scratch at its six waves per SIMD; here a chain, one wave's work however many waves there are, has four
+// (the CRC form: 120 VGPRs and no scratch; at five, 28 bytes).
+#ifndef SWC_DEFCHAIN_WAVES
+#define SWC_DEFCHAIN_WAVES 4
+#endif
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_DEFCHAIN_WAVES, SWC_DEFCHAIN_WAVES))) void swc_deflate_chain_kernel(Job* jobs, uint32_t n, WsMap wm) {
+    __shared__ __attribute__((aligned(16))) lzc::Lds<lzc::CfgDeflate::kWin> lds;
+    jobk::deflate_chains<lzc::CfgDeflate, false>(jobs, blockIdx.x, gridDim.x, n, wm, &lds, (int)threadIdx.x);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SWC_DEFCHAIN_WAVES, SWC_DEFCHAIN_WAVES))) void swc_deflate_chain_crc32_kernel(Job* jobs, uint32_t n, WsMap wm, uint32_t* __restrict__ crcs) {
+    __shared__ __attribute__((aligned(16))) lzc::Lds<lzc::CfgDeflate::kWin> lds;
+    jobk::deflate_chains<lzc::CfgDeflate, true>(jobs, blockIdx.x, gridDim.x, n, wm, &lds, (int)threadIdx.x, crcs, &g_crc_consts);
+}
+constexpr size_t kChainGrid = 4096;   // (what the chip holds at four waves per SIMD)
 // "lz_copier" (swc_set_tuning): 1 = lz_copy.h with the windows above (default), 0 = the byte-cell resolver of lz_resolve.h
 // (rounds 2-4) -- both produce the same bytes.
 static std::atomic<int> g_lz_copier{1};
@@ -208,6 +227,12 @@ static bool wave_copier(size_t n) {
 }
 static void launch_lz_copy(const Job* jobs, size_t n, const WsMap& wm, const uint32_t* order, hipStream_t stream) {
     hipLaunchKernelGGL(swc_lz_copy_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, jobs, (uint32_t)n, wm, order);
+}
+static void launch_deflate_chains(Job* jobs, size_t n, const WsMap& wm, uint32_t* crcs, hipStream_t stream) {
+    const size_t tiles = (n + kWave - 1) / kWave;
+    const dim3 grid((unsigned)(tiles < kChainGrid ? tiles : kChainGrid));
+    if (crcs) hipLaunchKernelGGL(swc_deflate_chain_crc32_kernel, grid, dim3(kWave), 0, stream, jobs, (uint32_t)n, wm, crcs);
+    else hipLaunchKernelGGL(swc_deflate_chain_kernel, grid, dim3(kWave), 0, stream, jobs, (uint32_t)n, wm);
 }
 
 // Optional per-kernel timing of the calling thread's last batch launch (bench.py: roofline per kernel).  HIP events on the
@@ -255,15 +280,20 @@ static void launch_inflate_phase2(Job* jobs, size_t n, const WsMap& wm, const ui
     if (wave_copier(n)) {
         if (crcs) {
             hipLaunchKernelGGL(swc_lz_copy_crc32_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, jobs, (uint32_t)n, wm, order, crcs);
+            launch_deflate_chains(jobs, n, wm, crcs, stream);
             g_pt.mark(stream);
             launch_crc32_group(jobs, n, crcs, stream);
             return;
         }
         launch_lz_copy(jobs, n, wm, order, stream);
+        launch_deflate_chains(jobs, n, wm, nullptr, stream);
         g_pt.mark(stream);
         return;
     }
+    // the chains of linked units (deflate_chain.h) take the wave copier whatever the size of the launch -- the byte-cell resolver knows
+    // no history -- and each kernel skips the other's jobs, as in launch_lz4
     hipLaunchKernelGGL(swc_lz_resolve_kernel, dim3((unsigned)n), dim3(kInflateResolveThreads), 0, stream, jobs, (uint32_t)n, wm, g_prof, order);
+    launch_deflate_chains(jobs, n, wm, nullptr, stream);
     g_pt.mark(stream);
     if (crcs) (void)launch_crc32(jobs, n, crcs, stream);   // (hipGetLastError in the caller)
 }

@@ -109,9 +109,12 @@ SWC_HD void copy_run(uint8_t* d, const uint8_t* s, uint32_t n) {
 // of a sequence is a running sum over the records of seq_bytes(literals, length) -- what a sequence in LZ4's short form takes --
 // and its literals lie lit_skip() behind S.  The parse (lz4_wave.h), which simulates this sum, leaves an ANCHOR (record index, S)
 // wherever the rule would go wrong; a group never reaches across an anchor, and one that starts at an anchor takes its S from it.
-template <typename CFG, typename P, int RM = 0>
+// HIST: the stream may have history in front of it (`start`): the LZ4 forms always, the literal-stream form where a Deflate unit is
+// linked to its predecessor (deflate_chain.h).
+template <typename CFG, typename P, int RM = 0, bool HIST = (RM != 0)>
 struct Copier {
     static constexpr bool R8 = RM == 1, R4 = RM == 2, INP = RM != 0;   // INP: the literals lie in the compressed block (`lits`), a run at g.loff
+    static constexpr bool HIS = HIST;
     SWC_HD static uint32_t seq_bytes(uint32_t li, uint32_t le) { return le ? 3u + li + (li >= 15u ? 1u : 0u) + (le >= 19u ? 1u : 0u) : li; }
     SWC_HD static uint32_t lit_skip(uint32_t li, uint32_t le) { return le ? 1u + (li >= 15u ? 1u : 0u) : 0u; }
     // the second field of the packed scan: literal bytes (the offset into the dense literal stream), R4: bytes of the sequence
@@ -161,13 +164,14 @@ struct Copier {
     gptr out;
     gcptr lits;        // the stream's dense literal stream (16-byte aligned base); R8: the compressed block
     P limit;           // bytes of `out` that exist: min(bytes produced, capacity)
-    // INP: HISTORY in front of the stream (an LZ4 block's adjacent prefix, the earlier blocks of its chain).  `out` is where the
+    // HIS: HISTORY in front of the stream (an LZ4 block's adjacent prefix, the earlier blocks of its chain, the units in front of a
+    // linked Deflate unit).  `out` is where the
     // history begins and the stream's own bytes begin at position `start`: a match that reaches in front of the block is an
     // ordinary FAR source, and no position is negative.  Everything below `start` was written, and has arrived, before run().
     P start = 0;
     static constexpr uint32_t kSeam = 528;   // bytes of history run() fetches into the window: more than a far read of a match piece (kMaxLen, dword steps) overshoots
     static_assert(kSeam >= lzr::kMaxLen + 16u && kSeam % 16u == 0u && kSeam + 16u + kSpanMax <= WIN, "the seam");
-    SWC_D P vlo() const { return INP ? (P)A + start : (P)A; }   // the lowest virtual position that is this stream's to write
+    SWC_D P vlo() const { return HIS ? (P)A + start : (P)A; }   // the lowest virtual position that is this stream's to write
     uint32_t nin;      // R8: bytes of `lits` that exist (the block's compressed size: nothing is read beyond it)
 
     // wave state (the same in every lane)
@@ -710,7 +714,7 @@ struct Copier {
 
     // a stream of a few bytes: one lane builds it in the window, byte by byte (the prefetches of run() read eight bytes that exist)
     SWC_D void tiny(const SWC_AS_GLOBAL uint32_t* recs, uint32_t nrec) {
-        const P st = INP ? start : (P)0;
+        const P st = HIS ? start : (P)0;
         const uint32_t lim = (uint32_t)(limit - st);   // < 64
         SIMT_BEGIN(t, W)
             if (t == 0) {
@@ -727,7 +731,7 @@ struct Copier {
                     }
                     for (uint32_t k = 0; k < li && pos < lim; k++, pos++, lp++) l->win[pos] = lits[lp];
                     for (uint32_t k = 0; k < le && pos < lim; k++, pos++)
-                        l->win[pos] = pos >= di ? l->win[pos - di] : INP && st + pos >= di ? (uint8_t)out[st + pos - di] /* the history */ : (uint8_t)0;
+                        l->win[pos] = pos >= di ? l->win[pos - di] : HIS && st + pos >= di ? (uint8_t)out[st + pos - di] /* the history */ : (uint8_t)0;
                 }
             }
         SIMT_END_WAVE
@@ -743,9 +747,9 @@ struct Copier {
         fv = 0;
         landed = 0;
         if (nrec == 0) return;
-        const P st = INP ? start : (P)0;
+        const P st = HIS ? start : (P)0;
         if (limit - st < 64u) { tiny(recs, nrec); return; }
-        if (INP && st != 0) {
+        if (HIS && st != 0) {
             // The window starts with the last bytes of the history, from HBM: the stream's first 16-byte line shares them, and a
             // far read that begins in front of the window may run a few bytes into it -- into bytes that are in HBM already.
             const P vs = (P)A + st;
@@ -849,36 +853,29 @@ using CfgLz4 = Cfg<SWC_LZC4_WIN, SWC_LZC4_SPAN, SWC_LZC4_KEEP, SWC_LZC4_LITP>;
 // One job: `ws` is the stream's workspace area of `area` bytes written by phase 1.  RM 1 (R8) / 2 (R4), LZ4: the literals are
 // fetched from the job's input; R8: the area holds the header and eight-byte records; R4: four-byte records, and the anchors where
 // the literal stream would be (their number in the header's pad0).
-// `hist` (RM != 0): bytes of history that lie in place in front of job.out (Copier::start).
-template <typename CFG, int RM = 0>
-SWC_D void copy_job(const Job& job, const uint8_t* ws, size_t area, Lds<CFG::kWin>* lds, uint32_t hist = 0) {
+// `hist` (HIST): bytes of history that lie in place in front of job.out (Copier::start) -- an LZ4 block's (RM != 0), those of a linked
+// Deflate unit (RM == 0: deflate_chain.h asks for the copier with history; every other caller gets the code it always ran).
+template <typename CFG, int RM, bool HIST, typename P>
+SWC_D void copy_stream(const Job& job, const uint8_t* ws, size_t lo, Lds<CFG::kWin>* lds, uint32_t hist, uint64_t limit) {
     const SWC_AS_GLOBAL lzr::StreamHeader* h = (const SWC_AS_GLOBAL lzr::StreamHeader*)ws;
+    const SWC_AS_GLOBAL uint32_t* recs = (const SWC_AS_GLOBAL uint32_t*)(ws + sizeof(lzr::StreamHeader));
+    Copier<CFG, P, RM, HIST> cp;
+    cp.l = lds;
+    cp.out = (gptr)job.out - (HIST ? hist : 0u);
+    cp.start = HIST ? hist : 0u;
+    cp.lits = RM != 0 ? (gcptr)job.in : (gcptr)ws + lo;
+    cp.nin = RM != 0 ? (uint32_t)job.in_len : 0xFFFFFFFFu;   // (blocks are addressed with 32-bit offsets: the parse rejects larger ones)
+    if (RM == 2) { cp.anc = (const SWC_AS_GLOBAL uint32_t*)(ws + lo); cp.nanc = h->pad0; }
+    cp.limit = (P)limit;
+    cp.run(recs, h->nrec);
+}
+template <typename CFG, int RM = 0, bool HIST = (RM != 0)>
+SWC_D void copy_job(const Job& job, const uint8_t* ws, size_t area, Lds<CFG::kWin>* lds, uint32_t hist = 0) {
     const size_t lo = lzr::lit_offset(area, job.out_cap);
     if (lo == 0) return;   // no literal stream: phase 1 reported SWC_E_NEED_WORKSPACE for this job
-    const uint64_t limit = (job.out_len < job.out_cap ? job.out_len : job.out_cap) + (RM != 0 ? hist : 0u);
-    const SWC_AS_GLOBAL uint32_t* recs = (const SWC_AS_GLOBAL uint32_t*)(ws + sizeof(lzr::StreamHeader));
-    gcptr lits = RM != 0 ? (gcptr)job.in : (gcptr)ws + lo;
-    if (limit < 0xFFF00000ull) {   // (positions, watermarks and their differences in 32 bits)
-        Copier<CFG, uint32_t, RM> cp;
-        cp.l = lds;
-        cp.out = (gptr)job.out - (RM != 0 ? hist : 0u);
-        cp.start = RM != 0 ? hist : 0u;
-        cp.lits = lits;
-        cp.nin = RM != 0 ? (uint32_t)job.in_len : 0xFFFFFFFFu;   // (blocks are addressed with 32-bit offsets: the parse rejects larger ones)
-        if (RM == 2) { cp.anc = (const SWC_AS_GLOBAL uint32_t*)(ws + lo); cp.nanc = h->pad0; }
-        cp.limit = (uint32_t)limit;
-        cp.run(recs, h->nrec);
-    } else {
-        Copier<CFG, uint64_t, RM> cp;
-        cp.l = lds;
-        cp.out = (gptr)job.out - (RM != 0 ? hist : 0u);
-        cp.start = RM != 0 ? hist : 0u;
-        cp.lits = lits;
-        cp.nin = RM != 0 ? (uint32_t)job.in_len : 0xFFFFFFFFu;
-        if (RM == 2) { cp.anc = (const SWC_AS_GLOBAL uint32_t*)(ws + lo); cp.nanc = h->pad0; }
-        cp.limit = limit;
-        cp.run(recs, h->nrec);
-    }
+    const uint64_t limit = (job.out_len < job.out_cap ? job.out_len : job.out_cap) + (HIST ? hist : 0u);
+    if (limit < 0xFFF00000ull) copy_stream<CFG, RM, HIST, uint32_t>(job, ws, lo, lds, hist, limit);   // (positions, watermarks and their differences in 32 bits)
+    else copy_stream<CFG, RM, HIST, uint64_t>(job, ws, lo, lds, hist, limit);
 }
 
 }  // namespace lzc

@@ -52,8 +52,8 @@ struct Job {
 
 // aux of an LZ4 block job (include/swc_hip.h: SWC_LZ4_LINKED, SWC_LZ4_STORED)
 constexpr int32_t kLz4Linked = 1, kLz4Stored = 2;
-// aux of a Deflate job (include/swc_hip.h: SWC_DEFLATE_JOINED, SWC_DEFLATE_OPEN)
-constexpr int32_t kDeflateJoined = 1, kDeflateOpen = 2;
+// aux of a Deflate job (include/swc_hip.h: SWC_DEFLATE_JOINED, SWC_DEFLATE_OPEN, SWC_DEFLATE_LINKED)
+constexpr int32_t kDeflateJoined = 1, kDeflateOpen = 2, kDeflateLinked = 4;
 
 // A kernel's results back to its entry of the job list (AUX: `aux` too -- bzip2's block CRC)
 template <bool AUX = false>

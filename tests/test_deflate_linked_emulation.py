@@ -1,0 +1,243 @@
+"""CPU tier of the Deflate units that share history (SWC_DEFLATE_LINKED): phase 1 with its 32,768 bytes of assumed history and the
+reach it notes (csrc/inflate_sync.h, one wave and the team), the placing scan, and the chain copy (csrc/deflate_chain.h, lz_copy.h)
+in the host emulation, under the three lane orders, in every arrangement of phase 2 and both orders of the bodies, against units
+built token by token, zlib's own sync-flushed output and the oracle (_deflate_linked_cases); the stand-alone program under ASan +
+UBSan on the same cases."""
+import os
+import subprocess
+import zlib
+
+import pytest
+
+import _deflate_linked_cases as L
+import _deflate_units_cases as K
+import _emu_deflate_linked as E
+
+ORDERS = [0, 1, 2]
+# (arrangement of phase 2, CRC tails): resolver + chain-only copier | wave copier + chain kernel | the same with the CRC-32 of every output
+PHASE2 = [(E.RESOLVER, False), (E.COPIER, False), (E.COPIER, True)]
+RUNS = L.directed_runs()
+
+
+@pytest.fixture(scope="module")
+def expected():
+    return {name: L.expect(run) for name, run in RUNS.items()}
+
+
+def check_run(name, units, exp, got, crc=False):
+    """Every job against what is expected of it, every joined job right behind what its predecessor says exists, the CRC-32 of what
+    lies at every job's `out`."""
+    at = 0
+    for k, (u, e, g) in enumerate(zip(units, exp, got)):
+        what = "%s unit %d" % (name, k)
+        st, n, cons, aux, out = e
+        gst, gn, gcons, gaux, rel, gout, reach, gcrc = g
+        assert gst == st, what
+        assert gaux == aux, what + ": aux"
+        if not u["aux"] & L.JOINED:
+            at = 0
+        if rel is None:   # (joined to nothing)
+            assert (st, gn, gcons) == (L.INVALID_ARGUMENT, 0, 0), what
+            continue
+        assert rel == at, what + ": not placed behind its predecessor"
+        if n is not None:
+            assert (gn, gcons) == (n, cons), what
+        if out is not None:
+            assert gout == out, what
+        if not u["aux"] & L.LINKED:
+            assert reach == 0, what + ": a reach noted for a job that is not linked"
+        if crc:
+            assert gcrc == zlib.crc32(gout), what + ": CRC-32"
+        at += min(gn, u["cap"])
+
+
+def run_all_ways(name, units, exp, misalign=0, orders=ORDERS):
+    for order in orders:
+        E.set_order(order)
+        try:
+            for team in (0, 1):
+                for arrangement, crc in PHASE2:
+                    for rev in (False, True):
+                        got = E.run_units(units, misalign=misalign, arrangement=arrangement, team=team, reversed_=rev, crc=crc)
+                        check_run("%s (order %d team %d arrangement %d crc %d reversed %d)" % (name, order, team, arrangement, crc, rev), units, exp, got, crc)
+        finally:
+            E.set_order(0)
+
+
+SMALL = [n for n in RUNS if not n.startswith(("saturation", "outside"))]
+
+
+@pytest.mark.parametrize("name", SMALL)
+def test_directed_runs(expected, name):
+    """The seam (a match (5, 1) as the unit's first token; a distance equal to every byte in front; one more: SWC_E_REF_TRAP, the sizes
+    kept, not a byte written), an overlapping match across it, a chain that restarts at a job without the bit (and a reach past that
+    job's `out`), a predecessor over capacity and a failed one (every unit keeps its sizes and its own status), units of 0 and 1 bytes,
+    the bit without JOINED -- each in the three lane orders, with both forms of phase 1, the three arrangements of phase 2, both
+    orders of the bodies, at two alignments."""
+    for mis in (0, 11):
+        run_all_ways(name, RUNS[name], expected[name], misalign=mis)
+
+
+def test_what_the_cases_are(expected):
+    """The expectations say what the case list promises."""
+    e = expected
+    assert [x[0] for x in e["seam-5-1"]] == [L.OK, L.OK] and [x[0] for x in e["seam-every-byte"]] == [L.OK, L.OK]
+    assert e["seam-one-more"][1][:3] == (L.REF_TRAP, 43, len(RUNS["seam-one-more"][1]["data"])) and e["seam-one-more"][1][4] == b"\xa5" * 43
+    assert e["seam-one-more"][2][0] == L.OK and e["seam-one-more"][2][4] is None
+    assert [x[0] for x in e["saturation-legal"]] == [L.OK] * 3 and [x[0] for x in e["saturation-trap"]] == [L.OK, L.OK, L.REF_TRAP]
+    assert sum(x[1] for x in e["saturation-trap"][:2]) == 32767
+    assert [x[0] for x in e["restart-legal"]] == [L.OK] * 5 and [x[0] for x in e["restart-trap"]] == [L.OK, L.OK, L.OK, L.REF_TRAP, L.OK]
+    assert [x[0] for x in e["predecessor-over-capacity"]] == [L.OK, L.CAPACITY, L.OK, L.OK] and e["predecessor-over-capacity"][1][1] == 1530
+    f = e["failed-in-mid-chain"]
+    assert f[1][0] not in (L.OK, L.REF_TRAP, L.CAPACITY) and f[1][1] is None and [x[0] for x in f[2:]] == [L.OK, L.OK] and f[3][1] == 15
+    assert [x[1] for x in e["zero-and-one"]] == [100, 0, 1, 45]
+    assert [x[0] for x in e["linked-not-joined"]] == [L.OK, L.INVALID_ARGUMENT, L.REF_TRAP, L.OK]
+
+
+@pytest.mark.parametrize("name", ["saturation-legal", "saturation-trap", "outside-the-window"])
+def test_long_histories(expected, name):
+    """Three units of about 20,000 bytes: distance 32,768 at the third unit's first byte with 40,000 bytes in front (legal) and with
+    32,767 (a trap); a match at position 7,000 with distance 7,100 -- its source in the history, far in front of the 6 KiB window."""
+    run_all_ways(name, RUNS[name], expected[name], misalign=5, orders=[2])
+    E.set_order(0)
+    got = E.run_units(RUNS[name], misalign=9)
+    E.set_order(1)
+    try:
+        assert E.run_units(RUNS[name], misalign=9, team=1) == got
+    finally:
+        E.set_order(0)
+    check_run(name, RUNS[name], expected[name], got)
+    if name == "saturation-legal":
+        assert got[2][6] == 32768 and got[1][6] == 0 and got[0][6] == 0      # the reach phase 1 noted
+    if name == "outside-the-window":
+        assert got[1][6] == 100
+
+
+def test_sixteen_residues():
+    """The first unit has 160 + r bytes, the second opens with a match into it and ends off a 16-byte line: both exact at every residue
+    of the seam, at four residues of the head, in both orders of the bodies, the 16 guard bytes on both sides untouched."""
+    runs = L.residue_runs()
+    exp = [L.expect(run) for run in runs]
+    units = [u for run in runs for u in run]
+    for mis in (0, 3, 8, 13):
+        for arrangement, crc in PHASE2:
+            for rev in (False, True):
+                got = E.run_units(units, misalign=mis, arrangement=arrangement, reversed_=rev, crc=crc)
+                for r, run in enumerate(runs):
+                    assert len(run[0]["data"]) and exp[r][1][0] == L.OK and (exp[r][0][1] + exp[r][1][1]) % 16 != 0
+                    check_run("residue %d at %d" % (r, mis), run, exp[r], got[2 * r:2 * r + 2], crc)
+
+
+def test_linked_job_0():
+    """Linked jobs nobody heads -- job 0 and what is joined to it -- report what joined jobs with no head report; the run behind them
+    is the oracle's."""
+    units = L.linked_job_0()
+    exp = L.expect(units)
+    assert [e[:3] for e in exp[:2]] == [(L.INVALID_ARGUMENT, 0, 0)] * 2 and [e[0] for e in exp[2:]] == [L.OK, L.OK]
+    run_all_ways("linked job 0", units, exp, misalign=6, orders=[0, 2])
+
+
+def test_chain_across_three_tiles():
+    """Sixty whole streams, then seventy tiny linked units: jobs 60 .. 129, a chain over two borders of the placing scan's tiles."""
+    jobs = L.tiles_run()
+    assert len(jobs) == 130 and all(u["aux"] & L.LINKED for u in jobs[61:]) and not jobs[60]["aux"] & L.JOINED
+    exp = [K.expect(dict(u, open_plain=None))[:5] for u in jobs[:60]] + L.expect(jobs[60:])
+    assert all(e[0] == L.OK for e in exp)
+    for order in ORDERS:
+        E.set_order(order)
+        try:
+            for arrangement, crc in PHASE2:
+                got = E.run_units(jobs, misalign=order * 5, arrangement=arrangement, team=order & 1, reversed_=order == 1, crc=crc)
+                for i in range(60):
+                    check_run("whole stream %d" % i, jobs[i:i + 1], exp[i:i + 1], got[i:i + 1], crc)
+                check_run("the chain", jobs[60:], exp[60:], got[60:], crc)
+        finally:
+            E.set_order(0)
+
+
+@pytest.fixture(scope="module")
+def sync_flushed():
+    """zlib's output, about 300 KiB of text flushed with Z_SYNC_FLUSH every 40,000 bytes, cut by swc_index_blocks with the new knob."""
+    from swcompression_amd import _lib, index_blocks
+    stream, plain = L.sync_flush_stream()
+    lib = _lib.load()
+    assert lib.swc_set_tuning(b"deflate_unit_bytes", 1) == 0 and lib.swc_set_tuning(b"deflate_units_linked", 1) == 0
+    try:
+        refs = index_blocks("deflate", stream)
+    finally:
+        lib.swc_set_tuning(b"deflate_unit_bytes", 0)
+        lib.swc_set_tuning(b"deflate_units_linked", 0)
+    units = L.units_of_refs(stream, refs, 40000 + 7)
+    return stream, plain, refs, units, L.expect(units)
+
+
+def test_real_encoder_output(sync_flushed):
+    """Every unit of the sync-flushed stream reaches into its predecessor; the run decodes to the plain text, unit by unit."""
+    stream, plain, refs, units, exp = sync_flushed
+    assert len(refs) == 8 and [r[3] for r in refs] == [L.OPEN] + [L.JL | L.OPEN] * 6 + [L.JL]
+    assert b"".join(e[4] for e in exp) == plain and all(e[0] == L.OK for e in exp)
+    for order, team, (arrangement, crc), rev in ((0, 0, PHASE2[1], False), (1, 1, PHASE2[2], True), (2, 0, PHASE2[0], True), (2, 1, PHASE2[1], False)):
+        E.set_order(order)
+        try:
+            got = E.run_units(units, misalign=3 + order, arrangement=arrangement, team=team, reversed_=rev, crc=crc)
+        finally:
+            E.set_order(0)
+        check_run("sync flush", units, exp, got, crc)
+        assert all(g[6] > 0 for g in got[1:]), "a unit of a sync-flushed text that reaches for nothing in front of it"
+
+
+def test_index_without_the_knob_is_unlinked():
+    from swcompression_amd import _lib, index_blocks
+    stream, _ = L.sync_flush_stream(total=90000)
+    lib = _lib.load()
+    assert lib.swc_set_tuning(b"deflate_unit_bytes", 1) == 0
+    try:
+        assert [r[3] for r in index_blocks("deflate", stream)] == [L.OPEN, L.JOINED | L.OPEN, L.JOINED]
+        assert lib.swc_set_tuning(b"deflate_units_linked", 2) != 0 and lib.swc_set_tuning(b"deflate_units_linked", -1) != 0
+        assert lib.swc_set_tuning(b"deflate_units_linked", 1) == 0
+        assert [r[3] for r in index_blocks("deflate", stream)] == [L.OPEN, L.JL | L.OPEN, L.JL]
+    finally:
+        lib.swc_set_tuning(b"deflate_unit_bytes", 0)
+        lib.swc_set_tuning(b"deflate_units_linked", 0)
+
+
+@pytest.mark.parametrize("arrangement,crc", PHASE2 + [(E.BODY_ALONE, False), (E.BODY_ALONE, True)])
+def test_unlinked_control(arrangement, crc):
+    """Every run of the units that stand alone (_deflate_units_cases.directed_runs) through the new bodies gives what it gives today --
+    the unit that reaches back still traps -- and no job that is not linked has a reach noted."""
+    runs = K.directed_runs()
+    units = [dict(u, ends_open=u["open_plain"] is not None) for run in runs.values() for u in run]
+    for order in ORDERS:
+        E.set_order(order)
+        try:
+            got = E.run_units(units, misalign=order, arrangement=arrangement, team=order & 1, crc=crc)
+        finally:
+            E.set_order(0)
+        i = 0
+        for name, run in runs.items():
+            exp = [K.expect(u) for u in run]
+            check_run(name, run, exp, got[i:i + len(run)], crc)
+            i += len(run)
+        assert all(g[6] == 0 for g in got)
+    assert K.expect(runs["reaches-back"][1])[0] == K.REF_TRAP
+
+
+def test_standalone_program_sanitized(tmp_path, expected, sync_flushed):
+    """tests/host_emu/emu_deflate_linked.cpp as a program of its own under ASan + UBSan on the same cases: 3 lane orders x both forms of
+    phase 1 x the three arrangements of phase 2 x both orders of the bodies x four alignments (the long cases: every combination once),
+    in allocations of exactly the lines the contract names."""
+    exe = str(tmp_path / "emu_deflate_linked")
+    E.compile_program(exe)
+    cases = [(RUNS[name], expected[name]) for name in RUNS]
+    for run in L.residue_runs()[::3]:
+        cases.append((run, L.expect(run)))
+    cases.append((L.linked_job_0(), L.expect(L.linked_job_0())))
+    jobs = L.tiles_run()
+    cases.append((jobs, [K.expect(dict(u, open_plain=None))[:5] for u in jobs[:60]] + L.expect(jobs[60:])))
+    cases.append((sync_flushed[3], sync_flushed[4]))
+    path = str(tmp_path / "cases.bin")
+    E.write_cases(path, cases)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
+    p = subprocess.run([exe, path], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=env)
+    assert p.returncode == 0, p.stdout.decode(errors="replace")[-4000:]
+    assert b"%d cases, 0 mismatches" % len(cases) in p.stdout

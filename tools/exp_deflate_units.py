@@ -5,6 +5,10 @@ synchronise and the copy of the result).
     own archive, device jobs   the same stream staged in HBM once, one launch of its units (DeviceBatch; the head owns the output)
     sync-flushed, host         a zlib Z_SYNC_FLUSH member of MIB / 8 MiB, flushed every 128 KiB: units that refer to each other, so
                                the run is refused and the stream decoded whole -- what the fallback costs
+    sync MIB MiB, ...          a Z_SYNC_FLUSH-every-128-KiB gzip member of MIB MiB -- what default pigz writes -- decoded three ways: with
+                               the knob off (one job), as units that stand alone (refused: the joined fallback), and as units that share
+                               history ("deflate_units_linked" = 1: one launch, the copy a chain on one wave); a library without the
+                               key runs the third row as the second
 
 Per shape one discarded warm-up call and STEPS timed calls: mean and sigma in ms, the launches and fallbacks one call issues
 (swc_stat), the result compared with the payload.  The units of the device-resident row are found HERE (the marker rule restated),
@@ -130,6 +134,17 @@ def main():
     sync = b"".join(c.compress(small[i:i + (128 << 10)]) + c.flush(zlib.Z_SYNC_FLUSH) for i in range(0, len(small), 128 << 10)) + c.flush()
     member = b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\xff" + sync + struct.pack("<II", zlib.crc32(small), len(small) & 0xFFFFFFFF)
     row("sync-flushed, host", lambda: swc.GzipArchive.unarchive(member), lambda r: r == small, len(small))
+
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    sync = b"".join(c.compress(payload[i:i + (128 << 10)]) + c.flush(zlib.Z_SYNC_FLUSH) for i in range(0, len(payload), 128 << 10)) + c.flush()
+    member = b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\xff" + sync + struct.pack("<II", crc, len(payload) & 0xFFFFFFFF)
+    del sync
+    for name, ub, linked in (("sync %d MiB, knob off" % mib, 0, 0), ("sync %d MiB, units joined" % mib, unit_bytes, 0), ("sync %d MiB, units linked" % mib, unit_bytes, 1)):
+        if has_units:
+            lib.swc_set_tuning(b"deflate_unit_bytes", ub)
+        lib.swc_set_tuning(b"deflate_units_linked", linked)      # (refused by a library without the key)
+        row(name, lambda: swc.GzipArchive.unarchive(member), lambda r: r == payload, len(payload))
+    lib.swc_set_tuning(b"deflate_units_linked", 0)
 
     res = {"label": label, "steps": steps, "mib": mib, "unit_bytes": unit_bytes if has_units else 0, "device": torch.cuda.get_device_name(0), "rows": rows}
     if out_path:
