@@ -40,7 +40,11 @@ typedef enum swc_codec {
     SWC_CODEC_LZ4_BLOCK = 2, /* one LZ4 block           -- LZ4.process(block:_:)    LZ4.swift:332-413; aux: swc_lz4_aux below */
     SWC_CODEC_LZMA2 = 3,   /* raw LZMA2 chunk stream   -- LZMA2Decoder.decode()    LZMA2Decoder.swift:34-99 */
     SWC_CODEC_LZMA = 4,    /* raw LZMA1 stream         -- LZMADecoder.decode()     LZMADecoder.swift:107-284*/
-    SWC_CODEC_BZIP2_BLOCK = 5, /* one bzip2 block body -- BZip2.decode(_:_:)       BZip2.swift:97-270       */
+    SWC_CODEC_BZIP2_BLOCK = 5, /* one bzip2 block body -- BZip2.decode(_:_:)       BZip2.swift:97-270; in / in_len = the stream (any
+                              bytes around the block), dict_len = BIT offset of the block body (behind the 48-bit magic and the
+                              stored CRC), dict (as an integer) = the stored CRC.  in_consumed is the BIT offset just behind the
+                              block.  aux is an OUT field, not read: the bzip2 CRC-32 of out[0 .. out_len) of a block that decoded
+                              (SWC_OK, SWC_E_BZIP2_WRONG_CRC), 0 after any other status                                      */
     SWC_CODEC_DELTA = 6,   /* XZ / 7-Zip Delta filter  -- DeltaFilter.decode(_:_:) DeltaFilter.swift:11-33; aux = distance as the
                               reference passes it (XZBlock.swift:57: property + 1), out may equal in            */
     SWC_CODEC_LZ4_COMPRESS = 7, /* ENCODE, one LZ4 block -- LZ4.compress(block:_:) LZ4+Compress.swift:157-281: in = prefix ++ block,
@@ -130,9 +134,9 @@ typedef struct swc_job {
     uint64_t out_len;     /* OUT: bytes produced; for SWC_E_CAPACITY on Deflate/LZ4: bytes required   */
     uint64_t in_consumed; /* OUT                                                                     */
     int32_t status;       /* OUT: swc_status                                                         */
-    int32_t aux;          /* IN : LZMA2 dictionary-size byte | LZMA props (lc | lp<<8 | pb<<16) | BZIP2: start bit (0..7) | LZ4: swc_lz4_aux bits | Deflate: swc_deflate_aux bits (OUT as well) */
+    int32_t aux;          /* IN : LZMA2 dictionary-size byte | LZMA props (lc | lp<<8 | pb<<16) | LZ4: swc_lz4_aux bits | Deflate: swc_deflate_aux bits (OUT as well) | BZIP2: OUT only, the CRC-32 of the block's output (swc_codec above) */
     const uint8_t* dict;  /* IN : LZ4 prefix dictionary (device) or NULL                             */
-    uint64_t dict_len;    /* IN : LZ4 dictionary length | LZMA: uncompressed size (UINT64_MAX = unknown) | LZMA dict size in the high half, see swc_hip.h notes */
+    uint64_t dict_len;    /* IN : LZ4 dictionary length | BZIP2: bit offset of the block body | LZMA: uncompressed size (UINT64_MAX = unknown) | LZMA dict size in the high half, see swc_hip.h notes */
 } swc_job;
 
 typedef struct swc_batch_opts {

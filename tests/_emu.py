@@ -78,26 +78,35 @@ class Guarded:
         assert C.string_at(end, back) == self._fill * back, "guard bytes behind overwritten (%s)" % what
 
 
-def run_batch(fn_name, inputs, caps, aux=None, dicts=None, extra=None, fn_args=(), dict_ptr_values=None, misalign=0, lib=None):
+def run_batch(fn_name, inputs, caps, aux=None, dicts=None, extra=None, fn_args=(), dict_ptr_values=None, misalign=0, lib=None,
+              in_misalign=None):
     """inputs: list[bytes]; caps: list[int].  Returns list of (status, out_bytes, in_consumed, out_len).
     misalign: the output buffers start that many bytes past a 16-byte boundary, 16 guard bytes on either side.  lib: another build
-    of the library (ASAN)."""
+    of the library (ASAN).  in_misalign (not None): the inputs -- and the dictionaries, seven residues further -- lie in guarded
+    buffers of their own that many bytes past a 16-byte boundary, and are checked unchanged afterwards."""
     n = len(inputs)
     jobs = (Job * n)()
-    keep, outs = [], []
+    keep, outs, ins = [], [], []
     for i, (data, cap) in enumerate(zip(inputs, caps)):
-        ib = C.create_string_buffer(bytes(data), max(len(data), 1))
-        keep.append(ib)
+        if in_misalign is None:
+            ib = C.create_string_buffer(bytes(data), max(len(data), 1))
+            keep.append(ib)
+        else:
+            ins.append((Guarded(len(data), in_misalign, data=data), bytes(data), "input of job %d" % i))
         outs.append(Guarded(cap, misalign))
-        jobs[i].in_ = C.addressof(ib)
+        jobs[i].in_ = C.addressof(ib) if in_misalign is None else ins[-1][0].addr
         jobs[i].in_len = len(data)
         jobs[i].out = outs[i].addr
         jobs[i].out_cap = cap
         jobs[i].aux = 0 if aux is None else aux[i]
         if dicts is not None and dicts[i] is not None:
-            db = C.create_string_buffer(bytes(dicts[i]), max(len(dicts[i]), 1))
-            keep.append(db)
-            jobs[i].dict = C.addressof(db)
+            if in_misalign is None:
+                db = C.create_string_buffer(bytes(dicts[i]), max(len(dicts[i]), 1))
+                keep.append(db)
+                jobs[i].dict = C.addressof(db)
+            else:
+                ins.append((Guarded(len(dicts[i]), (in_misalign + 7) % 16, data=dicts[i]), bytes(dicts[i]), "dictionary of job %d" % i))
+                jobs[i].dict = ins[-1][0].addr
             jobs[i].dict_len = len(dicts[i])
         if extra is not None:
             jobs[i].dict_len = extra[i]
@@ -105,34 +114,38 @@ def run_batch(fn_name, inputs, caps, aux=None, dicts=None, extra=None, fn_args=(
             jobs[i].dict = dict_ptr_values[i]
     getattr(lib or globals()["lib"], fn_name)(jobs, C.c_size_t(n), *fn_args)
     res = []
+    for buf, data, what in ins:
+        buf.check(what)
+        assert buf.read() == data, "%s changed" % what
     for i in range(n):
         outs[i].check("job %d" % i)
         res.append((jobs[i].status, outs[i].read(0, min(jobs[i].out_len, caps[i])), jobs[i].in_consumed, jobs[i].out_len))
     return res
 
 
-def inflate(inputs, caps, misalign=0):
+def inflate(inputs, caps, misalign=0, in_misalign=None):
     """Deflate: inflate_sync.h (one stream per wavefront, 64 sub-chunks at once) + lz_resolve.h."""
-    return run_batch("emu_inflate_sync", inputs, caps, misalign=misalign)
+    return run_batch("emu_inflate_sync", inputs, caps, misalign=misalign, in_misalign=in_misalign)
 
 
-def lz4_block(inputs, caps, dicts=None, misalign=0):
-    return run_batch("emu_lz4_block", inputs, caps, dicts=dicts, misalign=misalign)
+def lz4_block(inputs, caps, dicts=None, misalign=0, in_misalign=None, aux=None):
+    """aux: the swc_lz4_aux bits of every job (SWC_LZ4_STORED = 2: `in` is copied)."""
+    return run_batch("emu_lz4_block", inputs, caps, aux=aux, dicts=dicts, misalign=misalign, in_misalign=in_misalign)
 
 
 LZMA_MODE = 0   # 0: literal coders in LDS / cell-by-cell spill (kernel without a workspace); 1: LDS as a cache of four coders
 
 
-def lzma2(inputs, caps, dict_bytes, mode=None):
-    return run_batch("emu_lzma_mode", inputs, caps, aux=dict_bytes, fn_args=(C.c_int(1), C.c_int(LZMA_MODE if mode is None else mode)))
+def lzma2(inputs, caps, dict_bytes, mode=None, **place):
+    return run_batch("emu_lzma_mode", inputs, caps, aux=dict_bytes, fn_args=(C.c_int(1), C.c_int(LZMA_MODE if mode is None else mode)), **place)
 
 
-def lzma(inputs, caps, props, dict_sizes, sizes, mode=None):
-    """props: list of (lc, lp, pb); sizes: declared uncompressed size or -1."""
+def lzma(inputs, caps, props, dict_sizes, sizes, mode=None, **place):
+    """props: list of (lc, lp, pb); sizes: declared uncompressed size or -1.  place: misalign / in_misalign of run_batch."""
     aux = [lc | (lp << 8) | (pb << 16) for lc, lp, pb in props]
     extra = [s & 0xFFFFFFFFFFFFFFFF for s in sizes]
     return run_batch("emu_lzma_mode", inputs, caps, aux=aux, extra=extra, fn_args=(C.c_int(0), C.c_int(LZMA_MODE if mode is None else mode)),
-                     dict_ptr_values=dict_sizes)
+                     dict_ptr_values=dict_sizes, **place)
 
 
 _bzip2_team = None
@@ -145,12 +158,12 @@ def set_bzip2_team(mode):
     _bzip2_team = mode
 
 
-def bzip2_block(streams, body_bits, crcs, caps, lcap=1000000):
+def bzip2_block(streams, body_bits, crcs, caps, lcap=1000000, **place):
     """One bzip2 block per job: `streams[i]` is the whole stream, body_bits[i] the bit offset of the block body."""
     if _bzip2_team is not None:
         return run_batch("emu_bzip2_block_team", streams, caps, extra=body_bits, dict_ptr_values=crcs,
-                         fn_args=(C.c_size_t(lcap), C.c_int(_bzip2_team[0]), C.c_int(_bzip2_team[1])))
-    return run_batch("emu_bzip2_block", streams, caps, extra=body_bits, dict_ptr_values=crcs, fn_args=(C.c_size_t(lcap),))
+                         fn_args=(C.c_size_t(lcap), C.c_int(_bzip2_team[0]), C.c_int(_bzip2_team[1])), **place)
+    return run_batch("emu_bzip2_block", streams, caps, extra=body_bits, dict_ptr_values=crcs, fn_args=(C.c_size_t(lcap),), **place)
 
 
 lib.emu_checksum.argtypes = [C.c_int, C.c_void_p, C.c_size_t]
@@ -207,19 +220,33 @@ def delta(data, distance, in_place=False):
     return out.raw[:len(data)]
 
 
-def lz4_compress(blocks, prefixes=None, caps=None):
+def delta_placed(data, distance, in_misalign, misalign, in_place=False):
+    """delta() with the input and the output in guarded buffers at those residues mod 16 (in place: one buffer, at `misalign`); the
+    guards are checked, and the input where it is not the output."""
+    data = bytes(data)
+    out = Guarded(len(data), misalign, data=data if in_place else b"")
+    src = out if in_place else Guarded(len(data), in_misalign, data=data)
+    lib.emu_delta(C.c_char_p(src.addr), C.c_void_p(out.addr), len(data), distance)
+    out.check("delta output")
+    if not in_place:
+        src.check("delta input")
+        assert src.read() == data, "delta input changed"
+    return out.read()
+
+
+def lz4_compress(blocks, prefixes=None, caps=None, **place):
     """LZ4 block compression (lz4_comp.h): returns list of (status, compressed bytes, in_consumed, out_len)."""
     prefixes = prefixes or [b""] * len(blocks)
     ins = [bytes(p) + bytes(b) for p, b in zip(prefixes, blocks)]
     caps = caps or [len(b) + len(b) // 255 + 16 for b in blocks]
-    return run_batch("emu_lz4_compress", ins, caps, extra=[len(p) for p in prefixes])
+    return run_batch("emu_lz4_compress", ins, caps, extra=[len(p) for p in prefixes], **place)
 
 
-def deflate_compress(bufs, caps=None, aux=None):
+def deflate_compress(bufs, caps=None, aux=None, **place):
     """Deflate compression (deflate_comp.h): returns list of (status, compressed bytes, in_consumed, out_len).  aux[i] & 1: unit i
     is a segment of a longer stream (BFINAL clear, an empty stored block behind its block)."""
     caps = caps or [len(b) + len(b) // 8 + 32 for b in bufs]
-    return run_batch("emu_deflate_compress", [bytes(b) for b in bufs], caps, aux=aux)
+    return run_batch("emu_deflate_compress", [bytes(b) for b in bufs], caps, aux=aux, **place)
 
 
 def bzip2_compress(data, block_size=1):

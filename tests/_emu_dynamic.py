@@ -13,11 +13,11 @@ def set_order(order):
     lib.emu_set_order(C.c_int(order))
 
 
-def deflate_compress_dynamic(inputs, caps=None, aux=None):
+def deflate_compress_dynamic(inputs, caps=None, aux=None, **place):
     """Returns list of (status, stream, in_consumed, out_len); the guard bytes around every output are checked."""
     if caps is None:
         caps = [len(x) + len(x) // 8 + 32 for x in inputs]
-    return _emu.run_batch("emu_deflate_compress_dynamic", inputs, caps, aux=aux, lib=lib)
+    return _emu.run_batch("emu_deflate_compress_dynamic", inputs, caps, aux=aux, lib=lib, **place)
 
 
 def huffman(weights, max_len):
