@@ -25,7 +25,8 @@
 //
 // All 64 lanes share ONE set of tables in LDS: direct lookup tables (10 / 8 bits, 32-bit entries that carry everything a
 // step needs, laid out so that the position update, the table switch of a length code and the loop exit are one instruction
-// each -- see the entry layout below) and two-level SUBTABLES for the codes longer than that (184 entries in LDS, which
+// each -- see the entry layout below; where a length code, its extra bits and the distance code behind it all lie inside the
+// index, the entry is a PAIR and the match takes one step instead of two: 89 % of the matches of text) and two-level SUBTABLES for the codes longer than that (184 entries in LDS, which
 // covers text and most binary data; larger sets overflow to the workspace).  The input of a round is staged in LDS shifted
 // left by two bits, so that the funnel shift a lane reads its window with yields the table ADDRESS bits directly.
 // Sub-chunks are 17 dwords long: an odd stride keeps the 64 lanes on different LDS banks, and everything in LDS together is
@@ -73,7 +74,9 @@ static_assert(kSyncChunk % 4 == 0 && kSyncChunk >= 36, "sub-chunks are whole dwo
 //   [10:11] both set UNLESS this is a length symbol: the two bits by which the index masks of the two tables differ
 //   [12]    length symbol: the next code is a distance (the bit IS the byte offset of the distance table behind the lit/len table)
 //   [13]    literal
-//   [14:28] base value: the literal, the length base, the distance base - 1
+//   [14:28] base value: the literal, the length base, the distance base - 1, as MANTISSA [14:22] << SHIFT [23:26] (every
+//           distance base - 1 is 0..3 << 0..13, everything else is below 512 and has shift 0); [27] clear;
+//           [28] PAIR (below).  (-DSWC_SYNC_NO_PAIRS=1, the format without pairs: the base value itself, 15 bits.)
 //   [29]    distance symbol
 //   [30]    stop: the end-of-block symbol (n2 > 2) or no symbol the fast path takes (n2 == 2: no bits)
 //   [31]    set in length AND distance entries: added to a position it flips its top bit on at a length code and off again at the
@@ -81,9 +84,19 @@ static_assert(kSyncChunk % 4 == 0 && kSyncChunk >= 36, "sub-chunks are whole dwo
 //           entry adds bit 30 and thereby ends the loop as well.  (Entries of the distance table that stop carry bit 31 too.)
 // LINK (n2 == 0, bits 30 / 31 clear): [5:9] index width k of the subtable, [10:14] bits in front of it + 2 (12 / 10),
 //   [18:29] index of the subtable's first entry.
+// PAIR (bit 28; only in the direct lit/len table): a length code, its extra bits AND the distance code behind it, where all
+//   three lie inside the index (pair_entry below) -- a match in ONE step.  n2: all bits of the match (both codes, both sets
+//   of extra bits: at most 10 + 13) + 2; c2: the bits in front of the distance's extra bits + 2, so that bfe(bits4, 0, n2)
+//   >> c2 yields those as for any other symbol; [14:15] the mantissa of the distance base - 1 and [23:26] its shift;
+//   [16:22] the LENGTH -- its extra bits are index bits, so it is a constant of the entry (3..127: longer ones do not pair);
+//   the distance bit, both not-length bits, and neither the length bit nor the toggle bit nor stop: the next code is a
+//   lit/len code, and the position a pair leaves is a lit/len boundary like any other.
 // The window a lane looks at, `bits4`, is the stream from the symbol's first bit on, shifted LEFT by two (the stage is stored
 // that way): (bits4 & mask) | table is the LDS byte address of the entry, and the extra bits of the symbol are
 // bfe(bits4, 0, n2) >> c2.
+#ifndef SWC_SYNC_NO_PAIRS
+#define SWC_SYNC_NO_PAIRS 0   // 1: no pair entries and the 15-bit base value (the loops are then those of the format without pairs)
+#endif
 constexpr uint32_t kEntLenBit = (uint32_t)kSyncLitBits + 2u;
 constexpr uint32_t kEntNotLen = ((1u << (kSyncLitBits - kSyncDistBits)) - 1u) << (kSyncDistBits + 2), kEntLen = 1u << kEntLenBit, kEntLit = 1u << 13, kEntDist = 1u << 29, kEntStop = 1u << 30, kEntTog = 1u << 31;
 static_assert(kSyncLitBits > kSyncDistBits && kEntLenBit <= 12u, "the entry keeps bits 10 .. 12 for the table switch");
@@ -92,34 +105,69 @@ constexpr uint32_t kLitMask4 = ((1u << kSyncLitBits) - 1u) << 2, kDistMask4 = ((
 static_assert(kEntLen == 4u << kSyncLitBits, "the length flag is the byte offset of the distance table");
 static_assert((kLitMask4 & ~kEntNotLen) == kDistMask4, "the masks differ in the not-length bits");
 constexpr uint32_t kInvLit = 2u | kEntNotLen | kEntStop, kInvDist = kInvLit | kEntTog;
-// kind: 1 literal, 2 length, 3 end of block, 0 distance (value: the distance base itself)
-SWC_HD uint32_t make_entry(uint32_t clen, uint32_t ext, uint32_t kind, uint32_t value) {
+constexpr uint32_t kEntShShift = 23, kEntPairBit = 28, kEntPair = SWC_SYNC_NO_PAIRS ? 0u : 1u << kEntPairBit, kEntPairLenShift = 16, kPairLenMax = 127;
+// kind: 1 literal, 2 length, 3 end of block, 0 distance; the base value (the distance base - 1) is mant << sh
+SWC_HD uint32_t make_entry(uint32_t clen, uint32_t ext, uint32_t kind, uint32_t mant, uint32_t sh) {
     const uint32_t c = (clen + ext + 2u) | ((clen + 2u) << 5);
-    return kind == 1 ? c | kEntNotLen | kEntLit | (value << kEntBaseShift)
-         : kind == 2 ? c | kEntLen | kEntTog | (value << kEntBaseShift)
+    const uint32_t v = SWC_SYNC_NO_PAIRS ? (mant << sh) << kEntBaseShift : (mant << kEntBaseShift) | (sh << kEntShShift);
+    return kind == 1 ? c | kEntNotLen | kEntLit | v
+         : kind == 2 ? c | kEntLen | kEntTog | v
          : kind == 3 ? c | kEntNotLen | kEntStop
-                     : c | kEntNotLen | kEntDist | kEntTog | ((value - 1u) << kEntBaseShift);
+                     : c | kEntNotLen | kEntDist | kEntTog | v;
 }
 SWC_HD uint32_t ent_bits(uint32_t e) { return (e & 31u) - 2u; }
+SWC_HD uint32_t ent_code_bits(uint32_t e) { return ((e >> 5) & 31u) - 2u; }
 SWC_HD bool ent_is_eob(uint32_t e) { return (e & kEntStop) != 0u && (e & 31u) > 2u; }
 SWC_HD bool ent_is_link(uint32_t e) { return (e & kEntPosMask) == 0u; }
+// (Only for an entry that is NOT a link: a link's subtable index, [18:29], may have bit 28 set.  Every reader of `lut` resolves
+// links first -- entry_at, the mm == 0 path of the two loops, pair_entry's own tests -- and subtable entries never pair.)
+SWC_HD bool ent_is_pair(uint32_t e) { return (e & kEntPair) != 0u; }
+SWC_HD uint32_t ent_pair_len(uint32_t e) { return bfe32(e, kEntPairLenShift, 7); }
+// the base value of an entry (the passes that may branch; decode_chunk_prov has its own, branch-free form)
+SWC_HD uint32_t ent_base(uint32_t e) {
+    if (SWC_SYNC_NO_PAIRS) return bfe32(e, kEntBaseShift, 15);
+    return bfe32(e, kEntBaseShift, ent_is_pair(e) ? 2u : 9u) << bfe32(e, kEntShShift, 4);
+}
+// The PAIR entry that takes the place of the direct lit/len entry `e` at index `idx`, or 0 if it stays as it is.  `dlut`: the
+// finished direct distance table.  A pair is made exactly where the two steps it replaces would both have been answered by
+// the direct tables without a stop:
+//   - `e` is a length symbol 257..285 (not a link, not a stop: the end of the block, 286 / 287 and unused codes stay for the
+//     step that reports them) whose code and extra bits (nl) leave index bits over: the length is then known from `idx`;
+//   - of the r = kSyncLitBits - nl bits left, as many as the distance table has address its direct entry -- the bits beyond
+//     r read as zeros, which finds the true entry whenever the true code has d <= r bits (a code is known by its first d
+//     bits) and otherwise finds a longer code, a link or an unused slot: only a plain distance symbol 0..29 with d <= r pairs.
+// The pair's bits are at most kSyncLitBits + 13 = 23 of the 30 a window holds, fewer than the 48 of the longest match in two
+// steps that kSyncStage allows for.
+SWC_HD uint32_t pair_entry(uint32_t e, uint32_t idx, const uint32_t* dlut) {
+    if (SWC_SYNC_NO_PAIRS || ent_is_link(e) || (e & (kEntLen | kEntStop)) != kEntLen) return 0u;
+    const uint32_t nl = ent_bits(e), cl = ent_code_bits(e);
+    if (nl >= (uint32_t)kSyncLitBits) return 0u;
+    const uint32_t r = (uint32_t)kSyncLitBits - nl;
+    const uint32_t len = ent_base(e) + ((idx >> cl) & ((1u << (nl - cl)) - 1u));
+    if (len > kPairLenMax) return 0u;
+    const uint32_t de = dlut[(idx >> nl) & ((1u << kSyncDistBits) - 1u)];
+    if (ent_is_link(de) || (de & (kEntDist | kEntStop)) != kEntDist) return 0u;
+    const uint32_t d = ent_code_bits(de);
+    if (d > r) return 0u;
+    const uint32_t c2 = nl + d + 2u, n2 = c2 + (ent_bits(de) - d);
+    return n2 | (c2 << 5) | kEntNotLen | kEntDist | kEntPair | (len << kEntPairLenShift) | (de & ((3u << kEntBaseShift) | (15u << kEntShShift)));
+}
 
 // The entry of lit/len symbol `sym` (0..287) / distance symbol `sym` (0..31) with a code of `d` bits
 // (Deflate+Constants.swift: lengthBase / distanceBase as arithmetic).
 SWC_HD uint32_t entry_of_symbol(bool dist, uint32_t sym, uint32_t d) {
     if (!dist) {
-        if (sym < 256) return make_entry(d, 0, 1, sym);
-        if (sym == 256) return make_entry(d, 0, 3, 0);
+        if (sym < 256) return make_entry(d, 0, 1, sym, 0);
+        if (sym == 256) return make_entry(d, 0, 3, 0, 0);
         if (sym > 285) return kInvLit;           // 286, 287: the checked step reports wrongSymbol
         const uint32_t s = sym - 257u;
         const uint32_t e = s < 8 || s == 28 ? 0u : (s >> 2) - 1u;
         const uint32_t base = s < 8 ? 3u + s : s == 28 ? 258u : 3u + ((4u + (s & 3u)) << e);
-        return make_entry(d, e, 2, base);
+        return make_entry(d, e, 2, base, 0);
     }
     if (sym > 29) return kInvDist;               // 30, 31: wrongSymbol
     const uint32_t e = sym < 4 ? 0u : (sym >> 1) - 1u;
-    const uint32_t base = sym < 4 ? 1u + sym : 1u + ((2u + (sym & 1u)) << e);
-    return make_entry(d, e, 0, base);
+    return make_entry(d, e, 0, sym < 4 ? sym : 2u + (sym & 1u), e);   // distance base - 1 = sym, or (2 + sym % 2) << e
 }
 
 // The canonical tables the checked step decodes with (struct Table of round 1, now in the workspace): per length d the
@@ -332,6 +380,7 @@ SWC_D void table_from_counts(const uint32_t* cnt, SWC_AS_GLOBAL uint32_t* tb, ui
 //   C  in canonical order: codes that fit the direct table fill their slots; a longer code belongs to the subtable of its
 //      first 10 / 8 bits, whose width is set by the LAST (longest) code with that prefix -- prefixes do not decrease in
 //      canonical order, so "last" is a look at the next symbol -- and whose offset is a running sum over those;
+//   P  (between C and D) direct length entries whose distance code lies inside the index as well become PAIR entries;
 //   D  the long codes fill their subtable slots.
 SWC_D bool sync_tables_from_lengths(SyncLds* sl, const Spill sp, int literals, int distances, SubTab& st, SyncProf& pf) {
     SWC_SP(pf, 0)
@@ -449,6 +498,16 @@ SWC_D bool sync_tables_from_lengths(SyncLds* sl, const Spill sp, int literals, i
     SWC_AS_GLOBAL uint32_t* subg = used > kSubLds ? sp.sub : nullptr;
     st.g = subg;
     simt::wave_fence();
+#if !SWC_SYNC_NO_PAIRS
+    // ---- P: the second look at the direct lit/len entries, 16 per lane (pair_entry: a lane rewrites only what it read itself,
+    // and the distance table it consults is finished and stays as it is)
+    SIMT_BEGIN(t, N)
+        for (int i = t; i < (1 << kSyncLitBits); i += N) {
+            const uint32_t pe2 = pair_entry(sl->lut[i], (uint32_t)i, sl->lut + (1 << kSyncLitBits));
+            if (pe2 != 0u) sl->lut[i] = pe2;
+        }
+    SIMT_END
+#endif
     // ---- D: the subtables start out as "no symbol", then every long code fills its slots
     SIMT_BEGIN(t, N)
         for (uint32_t i = (uint32_t)t; i < used; i += (uint32_t)N) {
@@ -540,6 +599,10 @@ SWC_D void decode_chunk_prov(const SyncLds* sl, const SubTab st, uint32_t start,
     uint32_t c_notlen = kEntNotLen, c_dmask = kDistMask4;
     int32_t c_m256 = -256;
     SWC_OPAQUE(c_notlen); SWC_OPAQUE(c_dmask); SWC_OPAQUE(c_m256);
+#if !SWC_SYNC_NO_PAIRS
+    int32_t c_m4 = -4;
+    SWC_OPAQUE(c_m4);
+#endif
     if (chunk_end > in_bits) chunk_end = in_bits;          // (the zero fill behind the input is not worth decoding)
     const bool dead = start >= in_bits;                    // nothing left for this sub-chunk: the checked step says what that means
     // (the window of the NEXT step is read as soon as the position is known: its LDS latency runs under the bookkeeping)
@@ -556,20 +619,31 @@ SWC_D void decode_chunk_prov(const SyncLds* sl, const SubTab st, uint32_t start,
         { const uint32_t* w = (const uint32_t*)(sl->stage + ((pos >> 3) & 0x1FFCu)); w0 = w[0]; w1 = w[1]; }
         tm = and_or(e, c_notlen, c_dmask);
         tb = e & kEntLen;
+#if SWC_SYNC_NO_PAIRS
         const uint32_t val = (bfe32(bits4, 0, e) >> ((e >> 5) & 31u)) + bfe32(e, kEntBaseShift, 15);
+        const uint32_t mlen = plen;
+#else
+        // A PAIR is the step of its distance with the length the entry holds: `plen` is zero at every lit/len lookup, and `lp` is
+        // zero in every other entry, so mlen is the length of the match a distance or a pair completes.  The mantissa field of a
+        // pair holds the length above its two bits (lp * 4 comes off); everything below is as for a plain distance entry --
+        // `need` sees the distance before `nout` grows, the record takes `run`, `run` is cleared.
+        const uint32_t lp = bfe32(e, kEntPairLenShift, 7) & sbfe1(e, kEntPairBit);
+        const uint32_t val = lshl_add_v(mad24(lp, c_m4, bfe32(e, kEntBaseShift, 9)), bfe32(e, kEntShShift, 4), bfe32(bits4, 0, e) >> ((e >> 5) & 31u));
+        const uint32_t mlen = plen + lp;
+#endif
         // a literal enters the accumulator at the top (a shift by 0 bytes leaves it alone); the group it belongs to is rewritten
         const uint32_t lit1 = bfe32(e, 13, 1);
         lb = alignbyte32(val, lb, lit1);
         nl3 += lit1;
         const uint32_t dm = sbfe1(e, 29);
         if (((nl3 & 3u) | (lit1 << 2)) == 7u) store_u32(prov + lshl_add<6>(nl3 & ~3u, lbase), lb);   // a literal came in and completed its group (nl3 % 4 == 3)
-        if (dm != 0u) store_u32(prov + roff, lshl_add<7>(plen, lshl_add<16>(val, run)));   // a distance completes a record
+        if (dm != 0u) store_u32(prov + roff, lshl_add<7>(mlen, lshl_add<16>(val, run)));   // a distance completes a record
         roff = mad24(dm, c_m256, roff);
         if (NEED) {
             const int32_t nd = (int32_t)val - (int32_t)nout;   // this much output must exist in front of the sub-chunk
             need = (int32_t)bfi32(dm, (uint32_t)(nd > need ? nd : need), (uint32_t)need);
         }
-        nout += lit1 + plen;                               // (plen is zero except in the step of the distance)
+        nout += lit1 + mlen;                               // (mlen is zero except in the step of the distance)
         run = clear_if(dm, run + lit1);
         plen = val & sbfe1(e, kEntLenBit);
     } while ((int32_t)pos < (int32_t)chunk_end);
@@ -631,9 +705,12 @@ SWC_D void decode_chunk(const SyncLds* sl, const SubTab st, uint32_t start, uint
             else { pos += n; flags |= kFlagEob; }
             break;
         }
-        const bool was_dist = dist_next;
+        // (a PAIR entry is a length and its distance at once: the step of the distance, with the length the entry holds.  The
+        // test above has taken all its bits against the end of the input, as the two steps would have, one after the other.)
+        const bool was_dist = dist_next || ent_is_pair(e);
+        if (ent_is_pair(e)) plen = ent_pair_len(e);
         const uint32_t is_lit = (e >> 13) & 1u;
-        const uint32_t val = (bfe32(bits4, 0, e) >> ((e >> 5) & 31u)) + bfe32(e, kEntBaseShift, 15) + (was_dist ? 1u : 0u);   // literal, length or distance
+        const uint32_t val = (bfe32(bits4, 0, e) >> ((e >> 5) & 31u)) + ent_base(e) + (was_dist ? 1u : 0u);   // literal, length or distance
         if (MODE != 0 && was_dist && val > own + nout) {
             if (val > room + nout) { flags |= kFlagTrap; break; }
             if (val - (own + nout) > over) over = val - (own + nout);

@@ -129,6 +129,16 @@ SWC_HD uint32_t lshl_add(uint32_t a, uint32_t b) {
     return (a << K) + b;
 #endif
 }
+// the same with the shift in a register (only k % 32 counts)
+SWC_HD uint32_t lshl_add_v(uint32_t a, uint32_t k, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t d;
+    asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(k), "v"(b));
+    return d;
+#else
+    return (a << (k & 31u)) + b;
+#endif
+}
 // (a & m) | o as ONE instruction (v_and_or_b32) with both constants in registers (a VOP3 instruction of gfx9 takes no literal)
 SWC_HD uint32_t and_or(uint32_t a, uint32_t m, uint32_t o) {
 #if defined(__HIP_DEVICE_COMPILE__)
