@@ -179,6 +179,7 @@ int swc_batch_decompress_crc32_ws(int codec, swc_job* jobs, size_t n, void* work
  *   SWC_SUM_CRC64        CheckSums.crc64       CheckSums.swift:39-46  (XZArchive.swift:109-120)
  *   SWC_SUM_BZIP2_CRC32  CheckSums.bzip2crc32  CheckSums.swift:30-37  (BZip2.swift:81)
  *   SWC_SUM_XXH32        XxHash32.hash(seed 0) XxHash32.swift:24-83   (LZ4.swift:300,326)
+ *   (SHA-256             Sha256.hash           Sha256.swift:28-142    (XZArchive.swift:106-121): 32 bytes, swc_batch_sha256 below)
  * `jobs` and `sums` are device pointers. */
 typedef enum swc_checksum {
     SWC_SUM_CRC32 = 1,
@@ -188,6 +189,14 @@ typedef enum swc_checksum {
     SWC_SUM_XXH32 = 5
 } swc_checksum;
 int swc_batch_checksum(int kind, const swc_job* jobs, size_t n, uint64_t* sums, const swc_batch_opts* opts);
+
+/* SHA-256 (Sha256.hash(data:), reference Sources/Common/Sha256.swift:28-142, the block check of an .xz file of check type 0x0A as
+ * XZArchive.swift:106-121 verifies it) of every job's output, same coverage rule: digests[32 i .. 32 i + 32) is the digest of
+ * out[0 .. min(out_len, out_cap)) of job i, whatever its status, in the standard's byte order.  `jobs` and `digests` are device
+ * pointers, `digests` holds 32 * n bytes at any alignment.  A message is hashed by ONE lane (its blocks are one dependent chain):
+ * the throughput of a call is the number of its jobs, and a call lasts as long as its longest job.  (The sums of
+ * swc_batch_checksum are 64-bit: kind 6 stays SWC_E_INVALID_ARGUMENT there.) */
+int swc_batch_sha256(const swc_job* jobs, size_t n, uint8_t* digests, const swc_batch_opts* opts);
 
 /* ------------------------------------------------------------------------------------------------
  * Single-shot calls (host buffers in, malloc()ed host buffer out).
@@ -451,6 +460,10 @@ const char* swc_version(void);
  *                               SWC_DEFLATE_LINKED as well, all but the first: they share the history of the units in front of them, so
  *                               streams whose units reach back (default pigz, Z_SYNC_FLUSH) decode as units instead of falling back;
  *                               0 (default): units that stand alone, as before;
+ *   "sha256_device_min_units" = n >= 1   process-wide: the SHA-256 checks of .xz blocks (swc_xz_unarchive, swc_xz_split_unarchive,
+ *                               swc_unarchive_many kind 6) are computed on the device, behind the decode, when the launch that decodes the
+ *                               blocks ahead holds at least n of them; below, by swc_sha256 on the host as the walk reaches them
+ *                               (default 32, measured: DESIGN.md 4.3.1);
  *   "bgzf_round_members" = 1..16384   process-wide, for tests: members per round of swc_bgzf_archive (default 16384); the file is
  *                               the same bytes whatever the round size. */
 int swc_set_tuning(const char* key, int value);
@@ -467,7 +480,8 @@ int swc_last_phase_ms(float* ms, int cap);
 /* Process-wide launch statistics of the host framing layer (monotonic, for tests and tuning): "launches" = batched
  * launches issued by the single-shot / many-archive entry points, "units" = units decoded by them, "xz_cache_hits" =
  * .xz blocks the sequential walk took from the index-driven ahead-of-time batch, "deflate_unit_fallbacks" = Deflate streams that
- * were cut into units and had to be decoded whole after all.  Unknown key: -1. */
+ * were cut into units and had to be decoded whole after all, "sha256_device_units" = .xz blocks whose SHA-256 check the walk
+ * took from the device.  Unknown key: -1. */
 long long swc_stat(const char* key);
 
 #ifdef __cplusplus

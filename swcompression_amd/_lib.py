@@ -63,6 +63,7 @@ def load():
     sig("swc_batch_decompress", I, I, C.c_void_p, C.c_size_t, C.POINTER(SwcBatchOpts))
     sig("swc_batch_crc32", I, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(SwcBatchOpts))
     sig("swc_batch_checksum", I, I, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(SwcBatchOpts))
+    sig("swc_batch_sha256", I, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(SwcBatchOpts))
     sig("swc_batch_workspace_bytes", C.c_size_t, I, C.c_size_t, C.c_uint64)
     sig("swc_batch_decompress_ws", I, I, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(SwcBatchOpts))
     sig("swc_batch_decompress_crc32_ws", I, I, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(SwcBatchOpts))

@@ -195,6 +195,18 @@ class DeviceBatch:
             raise RuntimeError("swc_batch_checksum failed with status %d" % st)
         return d.cpu().numpy().view(np.uint64)
 
+    def sha256(self):
+        """SHA-256 of every job's output, computed on the device (swc_batch_sha256): one job per lane.  Returns a numpy uint8
+        array of shape (n, 32), row i the digest of job i in the standard's byte order."""
+        torch = self.torch
+        d = torch.empty(max(self.n, 1) * 32, dtype=torch.uint8, device=self.device)
+        opts = _lib.SwcBatchOpts(self.device.index if self.device.index is not None else -1,
+                                 torch.cuda.current_stream(self.device).cuda_stream, 1, 0)
+        st = self.lib.swc_batch_sha256(self.d_jobs.data_ptr(), self.n, d.data_ptr(), C.byref(opts))
+        if st:
+            raise RuntimeError("swc_batch_sha256 failed with status %d" % st)
+        return d.cpu().numpy()[:self.n * 32].reshape(self.n, 32)
+
     def wipe_results(self):
         """Zeroes every job's output range, the result fields of the job records and the CRC buffer (bench.py: what is
         verified after the timed region must come from the last timed step, not from the warm-up).  The CRC buffer no longer

@@ -153,8 +153,8 @@ void host_result_free(void* p) {
     free(p);
 }
 
-static std::atomic<long long> g_stats[4];
-void stat_add(int which, long long v) { if (which >= 0 && which < 4) g_stats[which] += v; }
+static std::atomic<long long> g_stats[5];
+void stat_add(int which, long long v) { if (which >= 0 && which < 5) g_stats[which] += v; }
 
 // What a thread keeps page-locked between calls, per direction.  Pinning is the expensive part of a large single-shot call
 // (a 268 MB result: tens of milliseconds to lock against 5 ms to copy), so a buffer that served an archive of a gigabyte
@@ -220,6 +220,7 @@ static void copy_out(std::vector<CopyOut>& v) {
     for (auto& x : th) x.join();
 }
 
+constexpr int kSumSha256 = 6;   // HostUnit::sum_kind: SHA-256 (host_util.h)
 static int run_units_impl(int codec, std::vector<HostUnit>& units);
 int run_units(int codec, std::vector<HostUnit>& units) {
     const int st = run_units_impl(codec, units);
@@ -319,7 +320,8 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
         int sum_kind = 0;
         for (size_t k = 0; k < m && !sum_kind; k++) sum_kind = units[pending[k]].sum_kind;
         const size_t jobs_bytes = (m * sizeof(Job) + 15) & ~(size_t)15, off_bytes = (ws_off.size() * sizeof(uint64_t) + 15) & ~(size_t)15;
-        const size_t sum_bytes = sum_kind ? (m * sizeof(uint64_t) + 15) & ~(size_t)15 : 0;
+        const size_t sum_each = sum_kind == kSumSha256 ? 32 : sizeof(uint64_t);   // (a SHA-256 digest: 32 bytes per unit, in the same copy down)
+        const size_t sum_bytes = sum_kind ? (m * sum_each + 15) & ~(size_t)15 : 0;
         const size_t in_bytes = in_total + 16;
         const size_t up_bytes = in_bytes + jobs_bytes + off_bytes;                 // host -> device
         const size_t down_bytes = jobs_bytes + off_bytes + sum_bytes + out_total;   // device -> host
@@ -375,7 +377,9 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
             if (launch_inflate(reinterpret_cast<Job*>(d_jobs), m, d_ws.ptr(), ws_bytes, stream, d_off, reinterpret_cast<uint32_t*>(d_sums)) != hipSuccess) return SWC_E_DEVICE;
         } else {
             if (launch_codec(codec, reinterpret_cast<Job*>(d_jobs), m, d_ws.ptr(), ws_bytes, stream, d_off) != hipSuccess) return SWC_E_DEVICE;
-            if (sum_kind && launch_checksum(sum_kind, reinterpret_cast<const Job*>(d_jobs), m, reinterpret_cast<uint64_t*>(d_sums), stream) != hipSuccess) return SWC_E_DEVICE;
+            if (sum_kind == kSumSha256) {
+                if (launch_sha256(reinterpret_cast<const Job*>(d_jobs), m, d_sums, stream) != hipSuccess) return SWC_E_DEVICE;
+            } else if (sum_kind && launch_checksum(sum_kind, reinterpret_cast<const Job*>(d_jobs), m, reinterpret_cast<uint64_t*>(d_sums), stream) != hipSuccess) return SWC_E_DEVICE;
         }
         stat_add(0, 1);
         stat_add(1, (long long)m);
@@ -391,6 +395,13 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
         const uint64_t* sums = reinterpret_cast<const uint64_t*>(down + jobs_bytes + off_bytes);
         const uint8_t* outs = down + jobs_bytes + off_bytes + sum_bytes;
 
+        // unit v's checksum from entry k of the checksum area, if the launch computed the kind it asked for
+        auto take_sum = [&](HostUnit& v, size_t k) {
+            if (!sum_kind || v.sum_kind != sum_kind) return;
+            if (sum_kind == kSumSha256) memcpy(v.digest, reinterpret_cast<const uint8_t*>(sums) + 32 * k, 32);
+            else v.sum = fused_crc ? reinterpret_cast<const uint32_t*>(sums)[k] : sums[k];
+            v.sum_valid = true;
+        };
         std::vector<size_t> next;
         std::vector<CopyOut> done;
         done.reserve(m);
@@ -415,7 +426,7 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
                     v.in_consumed = (size_t)jr.in_consumed;
                     v.need = jr.out_len;
                     v.out_size = produced;
-                    if (sum_kind && v.sum_kind == sum_kind) { v.sum = fused_crc ? reinterpret_cast<const uint32_t*>(sums)[k + r] : sums[k + r]; v.sum_valid = true; }
+                    take_sum(v, k + r);
                     if (kk != u.run_len) continue;
                     placed = placed && jr.out == d_out + out_off[k] + total;
                     total += produced;
@@ -477,7 +488,7 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
             const size_t produced = (size_t)std::min<uint64_t>(j.out_len, j.out_cap);
             u.out_size = produced;
             u.in_dst = u.dst != nullptr && produced <= u.dst_cap;
-            if (sum_kind && u.sum_kind == sum_kind) { u.sum = fused_crc ? reinterpret_cast<const uint32_t*>(sums)[k] : sums[k]; u.sum_valid = true; }
+            take_sum(u, k);
             done.push_back(CopyOut{&u, outs + out_off[k], produced});
         }
         copy_out(done);
@@ -509,6 +520,7 @@ int swc_set_tuning(const char* key, int value) try {
     if (!strcmp(key, "bgzf_round_members") && value >= 1 && value <= 16384) { set_bgzf_round_members(value); return SWC_OK; }
     if (!strcmp(key, "deflate_unit_bytes") && value >= 0) { set_deflate_unit_bytes(value); return SWC_OK; }
     if (!strcmp(key, "deflate_units_linked") && (value == 0 || value == 1)) { set_deflate_units_linked(value); return SWC_OK; }
+    if (!strcmp(key, "sha256_device_min_units") && value >= 1) { set_sha256_device_min_units(value); return SWC_OK; }
     if (!strcmp(key, "pinned_keep_mib") && value >= 0) { g_pinned_keep = (size_t)value << 20; return SWC_OK; }
     if (!strcmp(key, "result_cache_mib") && value >= 0) { g_result_cache = (size_t)value << 20; return SWC_OK; }
     if (!strcmp(key, "pool_keep_mib") && value >= 0) {   // applies to the current device at once, to the others when they are first used
@@ -534,6 +546,7 @@ long long swc_stat(const char* key) {
     if (!strcmp(key, "units")) return g_stats[1].load();
     if (!strcmp(key, "xz_cache_hits")) return g_stats[2].load();
     if (!strcmp(key, "deflate_unit_fallbacks")) return g_stats[3].load();
+    if (!strcmp(key, "sha256_device_units")) return g_stats[4].load();
     return -1;
 }
 
@@ -628,6 +641,18 @@ int swc_batch_checksum(int kind, const swc_job* jobs, size_t n, uint64_t* sums, 
     if (opts && opts->device >= 0 && hipSetDevice(opts->device) != hipSuccess) return SWC_E_DEVICE;
     hipStream_t stream = opts ? static_cast<hipStream_t>(opts->stream) : nullptr;
     if (launch_checksum(kind, reinterpret_cast<const Job*>(jobs), n, sums, stream) != hipSuccess) return SWC_E_DEVICE;
+    if (opts && opts->synchronize && hipStreamSynchronize(stream) != hipSuccess) return SWC_E_DEVICE;
+    return SWC_OK;
+} catch (...) {   // std::bad_alloc / length_error from a size taken from the input: never through the C boundary
+    return SWC_E_DEVICE;
+}
+
+int swc_batch_sha256(const swc_job* jobs, size_t n, uint8_t* digests, const swc_batch_opts* opts) try {
+    if (!device_ready()) return SWC_E_DEVICE;
+    if (n && (!jobs || !digests)) return SWC_E_INVALID_ARGUMENT;
+    if (opts && opts->device >= 0 && hipSetDevice(opts->device) != hipSuccess) return SWC_E_DEVICE;
+    hipStream_t stream = opts ? static_cast<hipStream_t>(opts->stream) : nullptr;
+    if (launch_sha256(reinterpret_cast<const Job*>(jobs), n, digests, stream) != hipSuccess) return SWC_E_DEVICE;
     if (opts && opts->synchronize && hipStreamSynchronize(stream) != hipSuccess) return SWC_E_DEVICE;
     return SWC_OK;
 } catch (...) {   // std::bad_alloc / length_error from a size taken from the input: never through the C boundary

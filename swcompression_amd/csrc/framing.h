@@ -39,6 +39,10 @@ void bzip2_collect_candidates(const uint8_t* d, size_t n, std::vector<HostUnit>&
 int bzip2_finish_stream(const uint8_t* d, size_t n, std::vector<HostUnit>& units, size_t first_unit, const std::vector<uint64_t>& used,
                         std::vector<uint8_t>& res, size_t& byte_pos);
 size_t lzma2_announced_size(const uint8_t* p, size_t n);
+void set_sha256_device_min_units(int v);   // "sha256_device_min_units" (swc_set_tuning)
+// XZArchive.unarchive of every archive of a set (framing_lzma.cpp): the blocks the indexes of ALL archives list decoded ahead in one
+// launch, then every archive walked on its own.  statuses[i] / outs[i] as swc_xz_unarchive leaves them; SWC_OK or SWC_E_DEVICE.
+int xz_run_many(const uint8_t* const* archives, const size_t* lens, size_t n, std::vector<int>& statuses, std::vector<std::vector<uint8_t>>& outs);
 // block discovery for swc_index_blocks (framing_many.cpp)
 struct BlockRef64 { uint64_t offset, comp_len, uncomp_len; uint32_t aux; uint32_t flags = 0; };
 bool bgzf_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out);

@@ -10,6 +10,7 @@
 // Headers, index, footer, padding and checks are verified on the host; every LZMA2 block body is a
 // unit of the batched device launch.
 #include <algorithm>
+#include <atomic>
 #include <map>
 #include <vector>
 #include "framing.h"
@@ -111,12 +112,25 @@ struct Predecoded {
     int prop;
     std::vector<uint8_t> out;
     size_t in_consumed;
-    int sum_kind = 0;        // swc_checksum kind of `sum` (1 CRC-32, 3 CRC-64), 0 = none: computed on the device behind the decode
+    int sum_kind = 0;        // swc_checksum kind of `sum` (1 CRC-32, 3 CRC-64) or 6 (SHA-256: `digest`), 0 = none: computed on the device behind the decode
     uint64_t sum = 0;
+    uint8_t digest[32] = {0};
 };
 // what xz_block knows about the data it appended beyond the bytes: a checksum the device computed (a block whose only filter
 // is LZMA2 and whose data were decoded ahead)
-struct BlockSum { int kind = 0; uint64_t sum = 0; };
+struct BlockSum { int kind = 0; uint64_t sum = 0; uint8_t digest[32] = {0}; };
+constexpr int kSumSha256 = 6;   // HostUnit::sum_kind (host_util.h)
+// "sha256_device_min_units": the fewest units of a run_units call whose SHA-256 checks the device computes.  MEASURED (DESIGN.md
+// 4.3.1, profiles/sha256.txt): a lane hashes 22 MB/s, a host thread 400 MB/s, so the launch needs 32 blocks to be ahead
+std::atomic<int> g_sha256_min_units{32};
+
+// the device kind of an .xz check type for a launch of `units` units, 0 = none
+int xz_sum_kind(int check_type, size_t units) {
+    if (check_type == 0x01) return 1;
+    if (check_type == 0x04) return 3;
+    if (check_type == 0x0A && units >= (size_t)g_sha256_min_units.load()) return kSumSha256;
+    return 0;
+}
 typedef std::map<int64_t, Predecoded> BlockCache;
 
 // XZBlock.init (XZBlock.swift:18-97).  Appends the block's data to `out`.
@@ -172,7 +186,7 @@ int xz_block(uint32_t header_size_byte, Reader& r, int check_size, std::vector<u
             // decoded ahead from exactly these bytes, cleanly: the same result the launch below would produce
             r.off += (int64_t)hit->second.in_consumed;
             next = std::move(hit->second.out);
-            if (bsum && filters_count == 1) { bsum->kind = hit->second.sum_kind; bsum->sum = hit->second.sum; }
+            if (bsum && filters_count == 1) { bsum->kind = hit->second.sum_kind; bsum->sum = hit->second.sum; memcpy(bsum->digest, hit->second.digest, 32); }
             cache->erase(hit);
             stat_add(2, 1);
         } else if (filters[i].id == 0x21) {
@@ -282,8 +296,9 @@ int xz_stream(Reader& r, std::vector<uint8_t>& out, bool& check_error, BlockCach
         } else if (check_type == 0x0A) {
             if (r.left() < 32) return SWC_E_REF_TRAP;
             uint8_t dg[32];
-            swc_sha256(bd, bl, dg);
-            const bool ok = memcmp(dg, r.d + r.off, 32) == 0;
+            if (bsum.kind == kSumSha256) stat_add(4, 1);
+            else swc_sha256(bd, bl, dg);
+            const bool ok = memcmp(bsum.kind == kSumSha256 ? bsum.digest : dg, r.d + r.off, 32) == 0;
             r.off += 32;
             if (!ok) { check_error = true; return SWC_OK; }
         }
@@ -375,57 +390,74 @@ static void xz_candidates(const uint8_t* d, size_t n, std::vector<Cand>& cands) 
     }
 }
 
-void xz_predecode(const uint8_t* d, size_t n, BlockCache& cache) {
-    std::vector<Cand> cands;
-    xz_candidates(d, n, cands);
-    if (cands.size() < 2) return;            // a single block gains nothing from being decoded ahead
-    // the blocks' check, if the streams of the archive agree on CRC-32 or CRC-64: on the device, behind the decode (a launch
-    // computes one kind; XZArchive.swift:106-121 on one host thread was as long as the launch itself)
-    int kind = cands[0].check_type == 0x01 ? 1 : cands[0].check_type == 0x04 ? 3 : 0;
-    for (const Cand& c : cands) if (c.check_type != cands[0].check_type) kind = 0;
-    std::vector<HostUnit> units(cands.size());
-    for (size_t k = 0; k < cands.size(); k++) {
-        HostUnit& u = units[k];
-        u.in = d + cands[k].data_off;
-        u.in_len = cands[k].len;
+// The candidates of one archive as units of a launch (the archive is their `base`: staged once); sum_kind where the unit's check is `kind`'s
+void xz_units(const uint8_t* d, size_t n, const std::vector<Cand>& cands, int kind, int kind_check_type, std::vector<HostUnit>& units) {
+    for (const Cand& c : cands) {
+        HostUnit u;
+        u.in = d + c.data_off;
+        u.in_len = c.len;
         u.base = d;
         u.base_len = n;
-        u.aux = cands[k].prop;
+        u.aux = c.prop;
         u.cap_hint = std::max<size_t>(lzma2_announced_size(u.in, u.in_len), 16);
-        u.sum_kind = kind;
+        u.sum_kind = c.check_type == kind_check_type ? kind : 0;
+        units.push_back(std::move(u));
     }
-    if (run_units(SWC_CODEC_LZMA2, units) != SWC_OK) return;
+}
+// ... and what the launch left of them, as the cache of that archive's walk: units[first + k] is candidate k
+void xz_cache_fill(const std::vector<Cand>& cands, std::vector<HostUnit>& units, size_t first, BlockCache& cache) {
     for (size_t k = 0; k < cands.size(); k++) {
-        if (units[k].status != SWC_OK) continue;
-        Predecoded p{cands[k].prop, std::move(units[k].out), units[k].in_consumed};
-        if (units[k].sum_valid) { p.sum_kind = kind; p.sum = units[k].sum; }
+        HostUnit& u = units[first + k];
+        if (u.status != SWC_OK) continue;
+        Predecoded p{cands[k].prop, std::move(u.out), u.in_consumed};
+        if (u.sum_valid) { p.sum_kind = u.sum_kind; p.sum = u.sum; memcpy(p.digest, u.digest, 32); }
         cache[cands[k].data_off] = std::move(p);
     }
 }
 
-int xz_run(const uint8_t* in, size_t in_len, std::vector<uint8_t>& all, std::vector<size_t>& sizes) {
-    Trace tr;
-    BlockCache cache_store;
-    xz_predecode(in, in_len, cache_store);
-    tr.mark("xz: blocks decoded ahead", in_len);
-    BlockCache* cache = &cache_store;
+void xz_predecode(const uint8_t* d, size_t n, BlockCache& cache) {
+    std::vector<Cand> cands;
+    xz_candidates(d, n, cands);
+    if (cands.size() < 2) return;            // a single block gains nothing from being decoded ahead
+    // the blocks' check, if the streams of the archive agree on it: on the device, behind the decode (a launch computes one kind;
+    // XZArchive.swift:106-121 on one host thread was as long as the launch itself) -- CRC-32, CRC-64, and SHA-256 from
+    // "sha256_device_min_units" blocks on
+    int kind = xz_sum_kind(cands[0].check_type, cands.size());
+    for (const Cand& c : cands) if (c.check_type != cands[0].check_type) kind = 0;
+    std::vector<HostUnit> units;
+    xz_units(d, n, cands, kind, cands[0].check_type, units);
+    if (run_units(SWC_CODEC_LZMA2, units) != SWC_OK) return;
+    xz_cache_fill(cands, units, 0, cache);
+}
+
+// The sequential walk of an archive (XZArchive.swift:27-51, :69-88) with the blocks in `cache` decoded ahead
+int xz_walk(const uint8_t* in, size_t in_len, BlockCache& cache, std::vector<uint8_t>& all, std::vector<size_t>& sizes) {
     size_t ahead = 0;
-    for (const auto& kv : cache_store) ahead += kv.second.out.size();
+    for (const auto& kv : cache) ahead += kv.second.out.size();
     all.reserve(ahead + 64);                 // (the result grows block by block: without this, by doubling and copying)
     Reader r{in, in_len, 0, false};
     while (!r.finished()) {
         if (r.left() < 32) { all.clear(); sizes.clear(); return SWC_E_XZ_WRONG_MAGIC; }  // :37
         bool check_error;
         const size_t start = all.size();
-        int st = xz_stream(r, all, check_error, cache);
+        int st = xz_stream(r, all, check_error, &cache);
         if (st) { all.clear(); sizes.clear(); return st; }
         sizes.push_back(all.size() - start);
         if (check_error) return SWC_E_XZ_WRONG_CHECK;                             // :44 carries the result so far
         st = xz_padding(r);
         if (st) { all.clear(); sizes.clear(); return st; }
     }
-    tr.mark("xz: the walk of the streams", all.size());
     return SWC_OK;
+}
+
+int xz_run(const uint8_t* in, size_t in_len, std::vector<uint8_t>& all, std::vector<size_t>& sizes) {
+    Trace tr;
+    BlockCache cache;
+    xz_predecode(in, in_len, cache);
+    tr.mark("xz: blocks decoded ahead", in_len);
+    const int st = xz_walk(in, in_len, cache, all, sizes);
+    tr.mark("xz: the walk of the streams", all.size());
+    return st;
 }
 
 }  // namespace
@@ -437,6 +469,42 @@ void xz_block_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& o
     xz_candidates(in, in_len, cands);
     for (const Cand& c : cands) out.push_back({(uint64_t)c.data_off, (uint64_t)c.len, (uint64_t)c.uncomp, (uint32_t)c.prop});
     std::sort(out.begin(), out.end(), [](const BlockRef64& a, const BlockRef64& b) { return a.offset < b.offset; });
+}
+
+void set_sha256_device_min_units(int v) { g_sha256_min_units = v; }
+
+// swc_unarchive_many kind 6.  Every .xz stream ends in an index, so the blocks of ALL archives -- single-block archives included -- are
+// known before anything is decoded: they go through ONE launch, each archive staged once as the `base` of its units.  The device
+// computes the check most candidates carry (a launch computes one kind); blocks with another check are summed by the walk on the
+// host, as are the blocks the walk has to decode itself (no index, a candidate that did not decode cleanly).
+int xz_run_many(const uint8_t* const* archives, const size_t* lens, size_t n, std::vector<int>& statuses, std::vector<std::vector<uint8_t>>& outs) {
+    std::vector<std::vector<Cand>> cands(n);
+    size_t total = 0, by_type[16] = {0};
+    for (size_t i = 0; i < n; i++) {
+        xz_candidates(archives[i], lens[i], cands[i]);
+        total += cands[i].size();
+        for (const Cand& c : cands[i]) by_type[c.check_type & 15]++;
+    }
+    int major = 0;
+    for (int t = 1; t < 16; t++) if (by_type[t] > by_type[major]) major = t;
+    std::vector<HostUnit> units;
+    units.reserve(total);
+    std::vector<size_t> first(n);
+    for (size_t i = 0; i < n; i++) {
+        first[i] = units.size();
+        xz_units(archives[i], lens[i], cands[i], xz_sum_kind(major, total), major, units);
+    }
+    if (!units.empty() && run_units(SWC_CODEC_LZMA2, units) != SWC_OK) return SWC_E_DEVICE;
+    statuses.assign(n, SWC_OK);
+    outs.assign(n, std::vector<uint8_t>());
+    for (size_t i = 0; i < n; i++) {
+        BlockCache cache;
+        xz_cache_fill(cands[i], units, first[i], cache);
+        std::vector<size_t> sizes;
+        statuses[i] = xz_walk(archives[i], lens[i], cache, outs[i], sizes);
+        if (statuses[i] == SWC_E_DEVICE) return SWC_E_DEVICE;
+    }
+    return SWC_OK;
 }
 
 // The chunk walk of LZMA2Decoder.decode() / dispatch() (reference Sources/LZMA2/LZMA2Decoder.swift:36-74) without the

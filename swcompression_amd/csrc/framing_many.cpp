@@ -142,17 +142,13 @@ int many_bzip2(const uint8_t* const* archives, const size_t* lens, size_t n, std
     return SWC_OK;
 }
 
-// kind 6: XZArchive.unarchive per archive.  Block boundaries of an .xz stream are only known block by block (or from the
-// index at its end), so every archive takes the single-archive path: one launch per block.
+// kind 6: XZArchive.unarchive per archive; the blocks the indexes of ALL archives list share one launch (framing_lzma.cpp)
 int many_xz(const uint8_t* const* archives, const size_t* lens, size_t n, std::vector<Result>& res) {
-    for (size_t i = 0; i < n; i++) {
-        uint8_t* o = nullptr;
-        size_t ol = 0;
-        res[i].status = swc_xz_unarchive(archives[i], lens[i], &o, &ol);
-        if (res[i].status == SWC_E_DEVICE) { swc_free(o); return SWC_E_DEVICE; }
-        res[i].data.assign(o, o + ol);
-        swc_free(o);
-    }
+    std::vector<int> statuses;
+    std::vector<std::vector<uint8_t>> outs;
+    const int st = xz_run_many(archives, lens, n, statuses, outs);
+    if (st) return st;
+    for (size_t i = 0; i < n; i++) { res[i].status = statuses[i]; res[i].data = std::move(outs[i]); }
     return SWC_OK;
 }
 

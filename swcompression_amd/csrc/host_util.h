@@ -87,13 +87,15 @@ struct HostUnit {
     uint8_t* dst = nullptr;
     size_t dst_cap = 0;
     // Optional: a checksum of the output computed ON THE DEVICE in the same launch sequence (swc_checksum kinds of
-    // include/swc_hip.h: 1 CRC-32, 2 Adler-32, 3 CRC-64, 4 bzip2 CRC-32, 5 XXH32); one kind per run_units call.
+    // include/swc_hip.h: 1 CRC-32, 2 Adler-32, 3 CRC-64, 4 bzip2 CRC-32, 5 XXH32; 6, internal: SHA-256, swc_batch_sha256's kernel);
+    // one kind per run_units call.
     int sum_kind = 0;
     // results
     std::vector<uint8_t> out;
     bool in_dst = false;         // the output is at `dst`, not in `out`
     size_t out_size = 0;         // bytes of output (wherever they are)
-    uint64_t sum = 0;            // the checksum, if sum_valid
+    uint64_t sum = 0;            // the checksum, if sum_valid (kinds 1-5)
+    uint8_t digest[32] = {0};    // the SHA-256, if sum_valid (kind 6)
     bool sum_valid = false;
     const uint8_t* data() const { return in_dst ? dst : out.data(); }
     size_t size() const { return in_dst ? out_size : out.size(); }
@@ -125,7 +127,7 @@ struct Trace {
 };
 
 // swc_stat counters (api.cpp)
-void stat_add(int which, long long v);   // 0 launches, 1 units, 2 xz_cache_hits, 3 deflate_unit_fallbacks
+void stat_add(int which, long long v);   // 0 launches, 1 units, 2 xz_cache_hits, 3 deflate_unit_fallbacks, 4 sha256_device_units
 
 }  // namespace swc
 #endif

@@ -28,6 +28,7 @@
 #include "crc32_group.h"
 #include "crc32_wave.h"
 #include "crc32_tail.h"
+#include "sha256_lane.h"
 
 namespace swc {
 
@@ -325,6 +326,16 @@ SWC_D void crc32_wave(const Job* __restrict__ jobs, uint32_t g, uint32_t* __rest
     if (len >= kCrcGroupLen) return;
     const uint32_t c = crcw::crc32_wave((gcptr)jobs[g].out, simt::uniform(len), consts);
     if (lane == 0) crcs[g] = c;
+}
+
+// ---- swc_sha256_kernel: one job per LANE.  digests + 32 g: the SHA-256 of what exists of job g's output, whatever its status, in
+// the standard's byte order; `digests` at any alignment
+SWC_D void sha256_lane(const Job* __restrict__ jobs, uint32_t g, uint8_t* __restrict__ digests) {
+    uint32_t h[8];
+    sha::sha256_lane((gcptr)jobs[g].out, made_bytes(jobs[g].out_len, jobs[g].out_cap), h);
+    gptr d = (gptr)digests + 32 * (size_t)g;
+    store_u128_a4(d, sha::be32(h[0]), sha::be32(h[1]), sha::be32(h[2]), sha::be32(h[3]));
+    store_u128_a4(d + 16, sha::be32(h[4]), sha::be32(h[5]), sha::be32(h[6]), sha::be32(h[7]));
 }
 
 }  // namespace jobk

@@ -749,6 +749,19 @@ __global__ __launch_bounds__(64) void swc_xxh32_kernel(const Job* __restrict__ j
     if (live && j == 0) sums[g] = h;
 }
 
+// SHA-256 (sha256_lane.h): 64 jobs per wave, one per lane; a wave runs as long as its longest job
+__global__ __launch_bounds__(64) void swc_sha256_kernel(const Job* __restrict__ jobs, uint32_t n, uint8_t* __restrict__ digests) {
+    const uint32_t g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= n) return;
+    jobk::sha256_lane(jobs, g, digests);
+}
+
+hipError_t launch_sha256(const Job* jobs, size_t n, uint8_t* digests, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(swc_sha256_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, jobs, (uint32_t)n, digests);
+    return hipGetLastError();
+}
+
 // ---- Delta filter, one stream per 256-thread workgroup ------------------------------------------
 __global__ __launch_bounds__(256) void swc_delta_kernel(Job* __restrict__ jobs, uint32_t n) {
     __shared__ delta::Lds<256> lds;

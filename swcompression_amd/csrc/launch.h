@@ -16,6 +16,8 @@ size_t inflate_ws_bytes_per_job(uint64_t cap);
 hipError_t launch_crc32(const Job* jobs, size_t n, uint32_t* crcs, hipStream_t stream);
 hipError_t launch_delta(Job* jobs, size_t n, hipStream_t stream);
 hipError_t launch_checksum(int kind, const Job* jobs, size_t n, uint64_t* sums, hipStream_t stream);
+// SHA-256 of every job's output (the coverage rule of the other sums): 32 bytes per job at `digests`, any alignment
+hipError_t launch_sha256(const Job* jobs, size_t n, uint8_t* digests, hipStream_t stream);
 void set_profile_buffer(void* p);
 void set_phase_timing(int on);
 void set_lzma_coder_cache(int on);

@@ -216,6 +216,7 @@ SWC_HD void store_u64_stream(gptr p, uint64_t v) {   // past the caches: for dat
 }
 struct __attribute__((packed, may_alias)) u128_any { uint32_t x, y, z, w; };
 SWC_HD void store_u128_a4(gptr p, uint32_t x, uint32_t y, uint32_t z, uint32_t w) { *(SWC_AS_GLOBAL u128_any*)p = u128_any{x, y, z, w}; }   // 16 bytes at any alignment
+SWC_HD u128_any load_u128(gcptr p) { return *(const SWC_AS_GLOBAL u128_any*)p; }   // likewise (global_load_dwordx4)
 
 // Workgroup barrier of the group-per-stream checksum kernels.  The host emulation build runs the T "threads" of a group
 // as real host threads and plugs its own barrier in here (tests/host_emu/emu.cpp).
