@@ -97,12 +97,23 @@ static_assert(kSyncChunk % 4 == 0 && kSyncChunk >= 36, "sub-chunks are whole dwo
 #ifndef SWC_SYNC_NO_PAIRS
 #define SWC_SYNC_NO_PAIRS 0   // 1: no pair entries and the 15-bit base value (the loops are then those of the format without pairs)
 #endif
+// The follow-up literal of decode_chunk_prov (there): -DSWC_SYNC_NO_FOLLOW=1 builds the loop with one code per step, as it was;
+// -DSWC_SYNC_FOLLOW_HELD=1 takes the follow-up's bits from the window the step already holds instead of the reloaded one (form
+// (b) of the measurement, profiles/follow_literal.txt).
+#ifndef SWC_SYNC_NO_FOLLOW
+#define SWC_SYNC_NO_FOLLOW 0
+#endif
+#ifndef SWC_SYNC_FOLLOW_HELD
+#define SWC_SYNC_FOLLOW_HELD 0
+#endif
+#define SWC_SYNC_FOLLOW (SWC_SYNC_NO_FOLLOW ? 0 : SWC_SYNC_FOLLOW_HELD ? 2 : 1)
 constexpr uint32_t kEntLenBit = (uint32_t)kSyncLitBits + 2u;
 constexpr uint32_t kEntNotLen = ((1u << (kSyncLitBits - kSyncDistBits)) - 1u) << (kSyncDistBits + 2), kEntLen = 1u << kEntLenBit, kEntLit = 1u << 13, kEntDist = 1u << 29, kEntStop = 1u << 30, kEntTog = 1u << 31;
 static_assert(kSyncLitBits > kSyncDistBits && kEntLenBit <= 12u, "the entry keeps bits 10 .. 12 for the table switch");
 constexpr uint32_t kEntBaseShift = 14, kEntPosMask = kEntTog | kEntStop | 31u;
 constexpr uint32_t kLitMask4 = ((1u << kSyncLitBits) - 1u) << 2, kDistMask4 = ((1u << kSyncDistBits) - 1u) << 2;
 static_assert(kEntLen == 4u << kSyncLitBits, "the length flag is the byte offset of the distance table");
+static_assert(((((uint32_t)kSyncLitBits + 2u) << 10) & kEntLen) != 0u && (kEntLit & (kEntLen | kEntNotLen)) == 0u, "a link has the literal bit AND the length bit, a literal only the first (the follow-up literal tells them apart by that)");
 static_assert((kLitMask4 & ~kEntNotLen) == kDistMask4, "the masks differ in the not-length bits");
 constexpr uint32_t kInvLit = 2u | kEntNotLen | kEntStop, kInvDist = kInvLit | kEntTog;
 constexpr uint32_t kEntShShift = 23, kEntPairBit = 28, kEntPair = SWC_SYNC_NO_PAIRS ? 0u : 1u << kEntPairBit, kEntPairLenShift = 16, kPairLenMax = 127;
@@ -578,7 +589,8 @@ SWC_D uint32_t walk_chunk(const SyncLds* sl, const SubTab st, uint32_t start, ui
 // checked after the scan (NEED = false: the round starts 32 KiB or more into the output, where no distance can fail).
 // A step stores what it completes: the literal accumulator (the newest byte at the top, four to a group) goes to the row of
 // its group when a literal fills the group (the last, incomplete group after the loop), a record to the row of the next
-// record when its distance comes in.  `run0`: literals in front of the sub-chunk that no record covers yet
+// record when its distance comes in.  A step takes the plain literal behind its own code as well (THE FOLLOW-UP LITERAL, in
+// the loop), so that sub-chunks of equal bits take about equal steps whatever they hold.  `run0`: literals in front of the sub-chunk that no record covers yet
 // (lane 0 of the first round of a block).  A sub-chunk that ends at the end-of-block symbol leaves its trailing literals
 // uncovered (`tail`), every other one closes them with a literal-only record.
 struct ProvOut {
@@ -591,9 +603,17 @@ template <bool NEED>
 SWC_D void decode_chunk_prov(const SyncLds* sl, const SubTab st, uint32_t start, uint32_t chunk_end, uint32_t in_bits, gptr prov,
                              uint32_t lane, uint32_t run0, ProvOut& r) {
     // (one base pointer for the wave and 32-bit offsets per lane: the stores take the base from scalar registers)
-    const uint32_t rbase = 4u * lane, lbase = (uint32_t)lzr::kProvRecBytes + 4u * lane;
+    const uint32_t rbase = 4u * lane;
+#if !SWC_SYNC_FOLLOW
+    const uint32_t lbase = (uint32_t)lzr::kProvRecBytes + 4u * lane;
+#endif
     uint32_t pos = start, tm = kLitMask4, tb = 0, e = 0;
+#if SWC_SYNC_FOLLOW
+    const uint32_t lbase4 = (uint32_t)lzr::kProvRecBytes - kProvRow + 4u * lane;   // the literal groups' rows, for a count that starts at 4
+    uint32_t plen = 0, run = run0, nl4 = 4, nout = 0, lb = 0;
+#else
     uint32_t plen = 0, run = run0, nl3 = 3, nout = 0, lb = 0;
+#endif
     uint32_t roff = rbase + kProvRow;                      // byte offset of my next record in the scratch (row 1 is the first)
     int32_t need = -0x40000000;
     uint32_t c_notlen = kEntNotLen, c_dmask = kDistMask4;
@@ -615,10 +635,39 @@ SWC_D void decode_chunk_prov(const SyncLds* sl, const SubTab st, uint32_t start,
         e = *(const uint32_t*)((const uint8_t*)sl->lut + and_or(bits4, tm, tb));
         uint32_t mm = e & kEntPosMask;
         if (mm == 0u) { SWC_SYNC_STAT(7, 1); SWC_SYNC_LONG(); e = long_lookup(sl, st, bits4, e); mm = e & kEntPosMask; }
+#if SWC_SYNC_FOLLOW == 2
+        const uint32_t wbase = pos & ~31u;                 // stream bit of w0's first bit (the held window: form (b) of the follow-up)
+#endif
         pos = pos + mm + 0xFFFFFFFEu;
+#if SWC_SYNC_FOLLOW == 2
+        // THE FOLLOW-UP LITERAL, from the window the step holds (see below): its index bits must lie inside w1:w0
+        const uint32_t fb4 = (uint32_t)((((uint64_t)w1 << 32) | w0) >> ((pos - wbase) & 63u));
+        const uint32_t fend = wbase + (65u - kEntLenBit) < chunk_end ? wbase + (65u - kEntLenBit) : chunk_end;
+#else
         { const uint32_t* w = (const uint32_t*)(sl->stage + ((pos >> 3) & 0x1FFCu)); w0 = w[0]; w1 = w[1]; }
+#endif
         tm = and_or(e, c_notlen, c_dmask);
         tb = e & kEntLen;
+#if SWC_SYNC_FOLLOW
+        // THE FOLLOW-UP LITERAL.  The step looks once more into the direct lit/len table, at the position it has just reached, and
+        // takes the code there if and only if the next turn would have decoded it as a plain literal: the lane is on the lit/len
+        // table and inside its sub-chunk -- ONE unsigned compare, a length that waits for its distance has flipped bit 31 of `pos`
+        // on and a stop has set bit 30 -- and the entry has the literal bit and not the length bit (a link to a subtable has both:
+        // kSyncLitBits + 2 in [10:14]; a literal with a longer code is left to the next step's long_lookup).  A sub-chunk of
+        // literals thereby takes as many steps as one of matches of the same number of bits, and the pass, which lasts as long as
+        // its busiest lane, gets shorter.  What is not taken reads as the entry "no bits, nothing": `fm`.
+        // The lane decodes exactly the codes it decoded one per step: `tm` / `tb` are those of a lit/len boundary already, `plen` is
+        // zero, `need` is not a literal's business, and `e` may stay the step's own entry -- it is looked at after the loop only
+        // if `pos` carries the stop bit, and a step that stops takes no follow-up.
+#if SWC_SYNC_FOLLOW != 2
+        const uint32_t fb4 = funnel32(w1, w0, pos);
+        const uint32_t fend = chunk_end;
+#endif
+        const uint32_t f = *(const uint32_t*)((const uint8_t*)sl->lut + (fb4 & kLitMask4));
+        const uint32_t fm = ((uint32_t)(pos < fend) & (uint32_t)((f & (kEntLit | kEntLen)) == kEntLit)) != 0u ? f : 2u;   // (a select: `&&` makes a region of it)
+        pos = pos + (fm & 31u) + 0xFFFFFFFEu;
+        { const uint32_t* w = (const uint32_t*)(sl->stage + ((pos >> 3) & 0x1FFCu)); w0 = w[0]; w1 = w[1]; }
+#endif
 #if SWC_SYNC_NO_PAIRS
         const uint32_t val = (bfe32(bits4, 0, e) >> ((e >> 5) & 31u)) + bfe32(e, kEntBaseShift, 15);
         const uint32_t mlen = plen;
@@ -634,21 +683,43 @@ SWC_D void decode_chunk_prov(const SyncLds* sl, const SubTab st, uint32_t start,
         // a literal enters the accumulator at the top (a shift by 0 bytes leaves it alone); the group it belongs to is rewritten
         const uint32_t lit1 = bfe32(e, 13, 1);
         lb = alignbyte32(val, lb, lit1);
-        nl3 += lit1;
         const uint32_t dm = sbfe1(e, 29);
+#if SWC_SYNC_FOLLOW
+        // Two literals may come in, and either may complete its group.  nl4 = nl3 + 1 counts the literals from 4: nl4 / 4 grows with
+        // every group, and as nl4 grows by two at the most, the old and the new value differ above bit 1 only then.  If the FIRST
+        // literal completed the group (nl4 % 4 is then 1: the second is in the next group already), the dword stored is the
+        // accumulator in front of the second shift.  The group's row is nl4 / 4 - 1 either way (`lbase4`).  ONE conditional region,
+        // as before.
+        const uint32_t lit2 = bfe32(fm, 13, 1), byte2 = fm >> kEntBaseShift, nl4_0 = nl4, litn = lit1 + lit2;
+        nl4 += litn;
+        if ((nl4 ^ nl4_0) > 3u) store_u32(prov + lshl_add<6>(nl4 & ~3u, lbase4), alignbyte32(byte2, lb, clear_if(nl4, lit2)));
+        lb = alignbyte32(byte2, lb, lit2);
+#else
+        nl3 += lit1;
+        const uint32_t litn = lit1;
         if (((nl3 & 3u) | (lit1 << 2)) == 7u) store_u32(prov + lshl_add<6>(nl3 & ~3u, lbase), lb);   // a literal came in and completed its group (nl3 % 4 == 3)
+#endif
         if (dm != 0u) store_u32(prov + roff, lshl_add<7>(mlen, lshl_add<16>(val, run)));   // a distance completes a record
         roff = mad24(dm, c_m256, roff);
         if (NEED) {
             const int32_t nd = (int32_t)val - (int32_t)nout;   // this much output must exist in front of the sub-chunk
             need = (int32_t)bfi32(dm, (uint32_t)(nd > need ? nd : need), (uint32_t)need);
         }
-        nout += lit1 + mlen;                               // (mlen is zero except in the step of the distance)
+        nout += litn + mlen;                               // (mlen is zero except in the step of the distance)
+#if SWC_SYNC_FOLLOW
+        run = bfi32(dm, lit2, run + litn);                 // (the follow-up literal lies behind the step's distance, in the next record's run)
+#else
         run = clear_if(dm, run + lit1);
+#endif
         plen = val & sbfe1(e, kEntLenBit);
     } while ((int32_t)pos < (int32_t)chunk_end);
+#if SWC_SYNC_FOLLOW
+    const uint32_t nlit = nl4 - 4u;
+    if (nlit & 3u) store_u32(prov + lshl_add<6>((nl4 & ~3u) + 4u, lbase4), lb);   // the last, incomplete group
+#else
     const uint32_t nlit = nl3 - 3u;
     if (nlit & 3u) store_u32(prov + lshl_add<6>(nl3 & ~3u, lbase), lb);   // the last, incomplete group
+#endif
     const uint32_t endb = pos & 0x3FFFFFFFu;
     uint32_t flags = 0;
     if (dead) flags = kFlagFail;
