@@ -126,6 +126,26 @@ typedef enum swc_deflate_aux {
     SWC_DEFLATE_LINKED = 4
 } swc_deflate_aux;
 
+/* aux of an SWC_CODEC_LZMA2 job: the dictionary-size byte in bits 0-7 (as ever), and above it the bit of a UNIT of a stream that
+ * was cut at a dictionary reset.  A chunk that resets the dictionary, the state and the properties (control >= 0xE0, or a stored
+ * chunk with control 1 in front of one that resets state and properties) starts a run of chunks that refers to nothing in front
+ * of it; swc_index_blocks kind 8 lists the runs.  A run that is not the last has no end marker:
+ *   SWC_LZMA2_OPEN: the unit may end without the end marker.  When the chunk loop (LZMA2Decoder.swift:36) is about to read a
+ *     control byte and the reader stands exactly at in_len -- and no byte past the end has been read -- the job ends with SWC_OK
+ *     and in_consumed = in_len.  At any other position the job behaves like any other (a chunk cut short: SWC_E_REF_TRAP).  aux is
+ *     an OUT field for this bit only, as for SWC_DEFLATE_OPEN: it stays set where the unit ended open and is cleared otherwise -- a
+ *     unit that met the end marker ends there like any stream; SWC_E_NEED_WORKSPACE leaves aux as it came, so that the same job
+ *     list can be launched again with a workspace.  in_len = 0 keeps its status.  No byte at or behind in + in_len is
+ *     read, with or without the bit: a unit lies in place inside its stream, the next run's control byte right behind it.
+ * A unit counts its output position from 0, and the literal coder and pos_state take their low bits from the position
+ * (LZMADecoder.swift:118,136): kind 8 cuts only where the announced sizes in front sum to a multiple of 16, which covers
+ * pb, lp <= 4.  A match that reaches in front of the unit fails in the unit (the whole stream may allow it): a caller accepts the
+ * units of a stream only if every unit but the last is SWC_OK, still OPEN, in_consumed == in_len and out_len == uncomp_len, and the
+ * last is SWC_OK; anything else, and the stream is decoded whole. */
+typedef enum swc_lzma2_aux {
+    SWC_LZMA2_OPEN = 0x100
+} swc_lzma2_aux;
+
 typedef struct swc_job {
     const uint8_t* in;    /* device pointer to the unit's compressed bytes                           */
     uint64_t in_len;
@@ -134,7 +154,7 @@ typedef struct swc_job {
     uint64_t out_len;     /* OUT: bytes produced; for SWC_E_CAPACITY on Deflate/LZ4: bytes required   */
     uint64_t in_consumed; /* OUT                                                                     */
     int32_t status;       /* OUT: swc_status                                                         */
-    int32_t aux;          /* IN : LZMA2 dictionary-size byte | LZMA props (lc | lp<<8 | pb<<16) | LZ4: swc_lz4_aux bits | Deflate: swc_deflate_aux bits (OUT as well) | BZIP2: OUT only, the CRC-32 of the block's output (swc_codec above) */
+    int32_t aux;          /* IN : LZMA2 dictionary-size byte, swc_lzma2_aux above it (OUT as well) | LZMA props (lc | lp<<8 | pb<<16) | LZ4: swc_lz4_aux bits | Deflate: swc_deflate_aux bits (OUT as well) | BZIP2: OUT only, the CRC-32 of the block's output (swc_codec above) */
     const uint8_t* dict;  /* IN : LZ4 prefix dictionary (device) or NULL                             */
     uint64_t dict_len;    /* IN : LZ4 dictionary length | BZIP2: bit offset of the block body | LZMA: uncompressed size (UINT64_MAX = unknown) | LZMA dict size in the high half, see swc_hip.h notes */
 } swc_job;
@@ -349,6 +369,15 @@ int swc_unarchive_many_devices(int kind, const uint8_t* const* archives, const s
  *           chunks that decodes on its own starts here), bit 1 = it carries a properties byte.  The end marker is not
  *           listed.  Returns SWC_E_LZMA2_WRONG_CONTROL_BYTE (:47-48) or SWC_E_REF_TRAP (a chunk runs past the buffer)
  *           with the chunks before the error in refs / *n.
+ *   kind 8  raw LZMA2 (first byte = dictionary-size byte): the UNITS the stream can be cut into at its dictionary resets
+ *           (swc_lzma2_aux).  With P = the sum of the unpack sizes the chunks in front of a chunk announce, a chunk is a cut
+ *           candidate iff P > 0, P % 16 == 0, and its control byte is >= 0xE0, or is 1 and the first chunk behind it that is not
+ *           stored (control >= 0x80), if there is one, has control >= 0xC0.  Candidates are merged until every unit but the last
+ *           holds at least "lzma2_run_bytes" compressed bytes (swc_set_tuning; 0: one unit).  offset from `in`; the last
+ *           unit runs to the end of the buffer; uncomp_len = the sum of the unit's announced sizes (exact for a unit that
+ *           decodes); aux = the dictionary-size byte | SWC_LZMA2_OPEN on all but the last; flags = 0.  A stream the walk cannot
+ *           follow (a wrong control byte, a chunk past the end) is ONE unit and SWC_OK: its decode reports the error.  The units
+ *           are candidates -- a match may reach behind a reset: a caller checks the result by the rule at swc_lzma2_aux.
  * *n receives the number found; up to `cap` are written. */
 typedef struct swc_block_ref {
     uint64_t offset;      /* bytes from `in` (kind 5: bits) */
@@ -460,6 +489,14 @@ const char* swc_version(void);
  *                               SWC_DEFLATE_LINKED as well, all but the first: they share the history of the units in front of them, so
  *                               streams whose units reach back (default pigz, Z_SYNC_FLUSH) decode as units instead of falling back;
  *                               0 (default): units that stand alone, as before;
+ *   "lzma2_run_bytes" = n >= 0   process-wide: the LZMA2 decoders (swc_lzma2_decompress, swc_lzma2_decompress_data, the blocks of
+ *                               swc_xz_unarchive / swc_xz_split_unarchive, swc_unarchive_many kinds 6 and 7, method 3 of
+ *                               swc_7z_unpack_folders) cut a stream at its dictionary resets (swc_index_blocks kind 8) into units
+ *                               of at least n compressed bytes that decode in parallel in one launch (swc_stat "lzma2_run_units");
+ *                               a stream whose units do not stand alone -- a match that reaches behind a reset, any error -- is
+ *                               decoded whole afterwards and that result is reported (swc_stat "lzma2_run_fallbacks");
+ *                               0 (default): never cut -- it ships as 0; flipping it is a follow-up that cites
+ *                               profiles/lzma2_runs.txt;
  *   "sha256_device_min_units" = n >= 1   process-wide: the SHA-256 checks of .xz blocks (swc_xz_unarchive, swc_xz_split_unarchive,
  *                               swc_unarchive_many kind 6) are computed on the device, behind the decode, when the launch that decodes the
  *                               blocks ahead holds at least n of them; below, by swc_sha256 on the host as the walk reaches them
@@ -481,7 +518,8 @@ int swc_last_phase_ms(float* ms, int cap);
  * launches issued by the single-shot / many-archive entry points, "units" = units decoded by them, "xz_cache_hits" =
  * .xz blocks the sequential walk took from the index-driven ahead-of-time batch, "deflate_unit_fallbacks" = Deflate streams that
  * were cut into units and had to be decoded whole after all, "sha256_device_units" = .xz blocks whose SHA-256 check the walk
- * took from the device.  Unknown key: -1. */
+ * took from the device, "lzma2_run_units" = the units of the LZMA2 streams that were cut at their dictionary resets and
+ * accepted, "lzma2_run_fallbacks" = LZMA2 streams that were cut and had to be decoded whole after all.  Unknown key: -1. */
 long long swc_stat(const char* key);
 
 #ifdef __cplusplus

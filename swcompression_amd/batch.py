@@ -30,6 +30,7 @@ class DeviceBatch:
     LZ4_LINKED, LZ4_STORED = 1, 2   # aux bits of an "lz4_block" job (include/swc_hip.h: swc_lz4_aux)
     DEFLATE_JOINED, DEFLATE_OPEN = 1, 2   # aux bits of a "deflate" job (swc_deflate_aux): the units of a stream cut at its flush points
     DEFLATE_LINKED = 4                    # ... together with DEFLATE_JOINED: the unit shares the history of the units in front of it
+    LZMA2_OPEN = 0x100                    # aux bit of an "lzma2" job above its dictionary-size byte (swc_lzma2_aux): a unit that ends without the end marker
 
     def __init__(self, codec, units, caps, aux=None, extra=None, dict_values=None, tile=1, device="cuda:0", replicate_inputs=True,
                  select=None, dicts=None, prefixes=None, guard=0):
@@ -79,7 +80,8 @@ class DeviceBatch:
         if dicts is not None or prefixes is not None or guard:
             assert tile == 1 and select is None
             aux_l = [0] * nd if aux is None else [int(a) for a in aux]
-            front = np.array([(0 if aux_l[i] & self.LZ4_LINKED else int(guard)) + (_align(len(prefixes[i])) if prefixes is not None and prefixes[i] else 0)
+            placed = self.codec in (CODECS["deflate"], CODECS["lz4_block"])   # (bit 0 of any other codec's aux is no link)
+            front = np.array([(0 if placed and aux_l[i] & self.LZ4_LINKED else int(guard)) + (_align(len(prefixes[i])) if prefixes is not None and prefixes[i] else 0)
                               for i in range(nd)], dtype=np.uint64)
             out_off = (np.concatenate([[0], np.cumsum(out_each + front)[:-1]]).astype(np.uint64) + front) if self.n else np.zeros(0, dtype=np.uint64)
             out_total = int((out_each + front).sum()) + int(guard)

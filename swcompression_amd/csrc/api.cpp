@@ -22,6 +22,7 @@ static_assert(sizeof(swc_job) == sizeof(swc::Job), "swc_job and swc::Job must ha
 static_assert(offsetof(swc_job, status) == offsetof(swc::Job, status), "layout");
 static_assert(offsetof(swc_job, dict_len) == offsetof(swc::Job, dict_len), "layout");
 static_assert(SWC_LZ4_LINKED == swc::kLz4Linked && SWC_LZ4_STORED == swc::kLz4Stored, "aux of an LZ4 block job");
+static_assert(SWC_LZMA2_OPEN == swc::kLzma2Open, "aux of an LZMA2 job");
 static_assert(SWC_DEFLATE_JOINED == swc::kDeflateJoined && SWC_DEFLATE_OPEN == swc::kDeflateOpen && SWC_DEFLATE_LINKED == swc::kDeflateLinked, "aux of a Deflate job");
 
 namespace swc {
@@ -153,8 +154,8 @@ void host_result_free(void* p) {
     free(p);
 }
 
-static std::atomic<long long> g_stats[5];
-void stat_add(int which, long long v) { if (which >= 0 && which < 5) g_stats[which] += v; }
+static std::atomic<long long> g_stats[7];
+void stat_add(int which, long long v) { if (which >= 0 && which < 7) g_stats[which] += v; }
 
 // What a thread keeps page-locked between calls, per direction.  Pinning is the expensive part of a large single-shot call
 // (a 268 MB result: tens of milliseconds to lock against 5 ms to copy), so a buffer that served an archive of a gigabyte
@@ -519,6 +520,7 @@ int swc_set_tuning(const char* key, int value) try {
     if (!strcmp(key, "bzip2_team_walk") && value >= 0 && value <= 2) { set_bzip2_team_walk(value); return SWC_OK; }
     if (!strcmp(key, "bgzf_round_members") && value >= 1 && value <= 16384) { set_bgzf_round_members(value); return SWC_OK; }
     if (!strcmp(key, "deflate_unit_bytes") && value >= 0) { set_deflate_unit_bytes(value); return SWC_OK; }
+    if (!strcmp(key, "lzma2_run_bytes") && value >= 0) { set_lzma2_run_bytes(value); return SWC_OK; }
     if (!strcmp(key, "deflate_units_linked") && (value == 0 || value == 1)) { set_deflate_units_linked(value); return SWC_OK; }
     if (!strcmp(key, "sha256_device_min_units") && value >= 1) { set_sha256_device_min_units(value); return SWC_OK; }
     if (!strcmp(key, "pinned_keep_mib") && value >= 0) { g_pinned_keep = (size_t)value << 20; return SWC_OK; }
@@ -547,6 +549,8 @@ long long swc_stat(const char* key) {
     if (!strcmp(key, "xz_cache_hits")) return g_stats[2].load();
     if (!strcmp(key, "deflate_unit_fallbacks")) return g_stats[3].load();
     if (!strcmp(key, "sha256_device_units")) return g_stats[4].load();
+    if (!strcmp(key, "lzma2_run_units")) return g_stats[5].load();
+    if (!strcmp(key, "lzma2_run_fallbacks")) return g_stats[6].load();
     return -1;
 }
 

@@ -21,6 +21,11 @@ int run_deflate_one(HostUnit& u);
 int run_deflate_one_bounded(HostUnit& u, size_t bound);
 void set_deflate_unit_bytes(int v);   // "deflate_unit_bytes" (swc_set_tuning)
 void set_deflate_units_linked(int v); // "deflate_units_linked" (swc_set_tuning)
+// LZMA2 streams through the engine, each cut into parallel units at its dictionary resets where it has any (framing_lzma.cpp);
+// what run_units(SWC_CODEC_LZMA2, ...) would leave in every stream, in one launch wherever no stream has to fall back
+int run_lzma2(std::vector<HostUnit>& streams);
+int run_lzma2_one(HostUnit& u);
+void set_lzma2_run_bytes(int v);      // "lzma2_run_bytes" (swc_set_tuning)
 void set_bgzf_round_members(int v);   // "bgzf_round_members" (swc_set_tuning): members per round of swc_bgzf_archive
 // many-archive batching helpers (framing_many.cpp)
 struct Lz4Plan {
@@ -52,5 +57,8 @@ bool lz4_frame_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& 
 void bzip2_magic_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out);
 void xz_block_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out);
 int lzma2_chunk_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out);
+int lzma2_chunk_walk(const uint8_t* in, size_t in_len, size_t p, std::vector<BlockRef64>& out);
+void lzma2_unit_index(const uint8_t* in, size_t in_len, size_t first, uint8_t dict_byte, size_t run_bytes, std::vector<BlockRef64>& out);
+size_t lzma2_run_bytes();
 }
 #endif

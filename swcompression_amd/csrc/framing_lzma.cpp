@@ -87,7 +87,7 @@ size_t lzma2_announced_size(const uint8_t* p, size_t n) {
 namespace {
 
 int run_lzma_unit(int codec, HostUnit& u) {
-    int st = run_one(codec, u);
+    int st = codec == SWC_CODEC_LZMA2 ? run_lzma2_one(u) : run_one(codec, u);
     if (st) return st;
     return SWC_OK;
 }
@@ -426,7 +426,7 @@ void xz_predecode(const uint8_t* d, size_t n, BlockCache& cache) {
     for (const Cand& c : cands) if (c.check_type != cands[0].check_type) kind = 0;
     std::vector<HostUnit> units;
     xz_units(d, n, cands, kind, cands[0].check_type, units);
-    if (run_units(SWC_CODEC_LZMA2, units) != SWC_OK) return;
+    if (run_lzma2(units) != SWC_OK) return;   // (blocks x runs in the one launch)
     xz_cache_fill(cands, units, 0, cache);
 }
 
@@ -494,7 +494,7 @@ int xz_run_many(const uint8_t* const* archives, const size_t* lens, size_t n, st
         first[i] = units.size();
         xz_units(archives[i], lens[i], cands[i], xz_sum_kind(major, total), major, units);
     }
-    if (!units.empty() && run_units(SWC_CODEC_LZMA2, units) != SWC_OK) return SWC_E_DEVICE;
+    if (!units.empty() && run_lzma2(units) != SWC_OK) return SWC_E_DEVICE;
     statuses.assign(n, SWC_OK);
     outs.assign(n, std::vector<uint8_t>());
     for (size_t i = 0; i < n; i++) {
@@ -516,7 +516,10 @@ int xz_run_many(const uint8_t* const* archives, const size_t* lens, size_t n, st
 // buffer (the reference would read out of range) is SWC_E_REF_TRAP.  Refs found before the error stay in `out`.
 int lzma2_chunk_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out) {
     if (in_len < 1) return SWC_E_REF_TRAP;
-    size_t p = 1;
+    return lzma2_chunk_walk(in, in_len, 1, out);
+}
+// ... from offset `p` of the buffer on (1: behind a dictionary-size byte; 0: the chunks alone, as the jobs take them)
+int lzma2_chunk_walk(const uint8_t* in, size_t in_len, size_t p, std::vector<BlockRef64>& out) {
     for (;;) {
         if (p >= in_len) return SWC_E_REF_TRAP;
         const uint8_t control = in[p];
@@ -539,6 +542,157 @@ int lzma2_chunk_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>&
         out.push_back(BlockRef64{p, hdr + comp, unpack, control, (reset == 3 ? 1u : 0u) | (reset >= 2 ? 2u : 0u)});
         p += hdr + comp;
     }
+}
+
+// ---- streams cut at their dictionary resets -----------------------------------------------------------------------------------
+// A chunk that resets the dictionary, the state and the properties starts a run of chunks that refers to nothing in front of it
+// (what the multi-threaded LZMA2 encoders write once per encoder block, and what a concatenation of payloads holds).  A stream is
+// CUT in front of such chunks into units that decode in parallel (include/swc_hip.h: SWC_LZMA2_OPEN).  A unit counts its output
+// position from 0, and pos_state and the literal-coder index are the low bits of the position (LZMADecoder.swift:118,136): with
+// fresh cells a constant shift only renames them, but the reference's trap at state 11 / pos_state 15 is tied to the absolute
+// position, so a cut is taken only where the announced sizes in front sum to a multiple of 16 (pb, lp <= 4) -- there a unit is
+// step for step what the stream does.  A stored chunk with control 1 resets the dictionary only: the model goes on behind it unless
+// the next chunk that is not stored resets state and properties (control >= 0xC0) -- only then is it a cut.
+// The cuts are candidates: a match may reach behind a reset (legal in the reference, LZMADecoder.swift:269,297; it fails in a
+// unit, whose checks are at least as strict as the stream's).  The result of the units stands only if every unit but the last
+// ended open exactly at its last byte with SWC_OK and exactly its announced size, and the last is SWC_OK; anything else and the
+// stream is decoded whole, as ever, and THAT result is reported -- error order, error-carried data and the quirks stay exact.
+// "lzma2_run_bytes": the least compressed size of a unit, 0 = never cut.  It ships as 0 -- the host paths decode as they always
+// did; flipping it is a follow-up that cites profiles/lzma2_runs.txt (tools/exp_lzma2_runs.py).
+static std::atomic<size_t> g_lzma2_run_bytes{0};
+void set_lzma2_run_bytes(int v) { g_lzma2_run_bytes = (size_t)v; }
+size_t lzma2_run_bytes() { return g_lzma2_run_bytes.load(); }
+
+// The units of one raw stream (swc_index_blocks kind 8); the chunks start at in[first] (1: behind the dictionary-size byte, 0: the
+// chunks alone), offsets count from `in`.  Always at least one unit; aux = dict_byte | the bit of its job.
+void lzma2_unit_index(const uint8_t* in, size_t len, size_t first, uint8_t dict_byte, size_t run_bytes, std::vector<BlockRef64>& out) {
+    std::vector<BlockRef64> chunks;
+    const size_t from = std::min(first, len);
+    const bool walked = len > from && lzma2_chunk_walk(in, len, from, chunks) == SWC_OK;
+    uint64_t announced = 0;   // P: the sizes announced in front of chunk c
+    uint64_t unit_start = from, unit_p = 0;
+    if (walked && run_bytes != 0)
+        for (size_t c = 0; c < chunks.size(); c++) {
+            const uint32_t control = chunks[c].aux;
+            bool cut = announced > 0 && announced % 16 == 0 && (control >= 0xE0 || control == 1);
+            if (cut && control == 1) {
+                size_t k = c + 1;
+                while (k < chunks.size() && chunks[k].aux < 0x80) k++;
+                cut = k == chunks.size() || chunks[k].aux >= 0xC0;
+            }
+            if (cut && chunks[c].offset - unit_start >= run_bytes) {
+                out.push_back({unit_start, chunks[c].offset - unit_start, announced - unit_p, (uint32_t)dict_byte | (uint32_t)SWC_LZMA2_OPEN});
+                unit_start = chunks[c].offset;
+                unit_p = announced;
+            }
+            announced += chunks[c].uncomp_len;
+        }
+    else
+        for (const BlockRef64& c : chunks) announced += c.uncomp_len;
+    out.push_back({unit_start, len - unit_start, announced - unit_p, (uint32_t)dict_byte});
+}
+
+int run_lzma2(std::vector<HostUnit>& streams) {
+    const size_t rb = g_lzma2_run_bytes.load();
+    struct Run { size_t stream, first, count; };
+    std::vector<Run> runs;
+    std::vector<std::vector<BlockRef64>> refs(streams.size());
+    if (rb != 0)
+        for (size_t s = 0; s < streams.size(); s++) {
+            const HostUnit& u = streams[s];
+            if (u.in_len <= rb || u.dict || u.chain || (u.aux & ~0xFF) != 0) continue;
+            lzma2_unit_index(u.in, u.in_len, 0, (uint8_t)u.aux, rb, refs[s]);
+            uint64_t total = 0;
+            for (const BlockRef64& r : refs[s]) total += r.uncomp_len;
+            // (exact capacities are taken as they are: the announced sizes of a damaged stream must not size the launch)
+            if (refs[s].size() >= 2 && total <= std::max<uint64_t>((uint64_t)64 << 20, (uint64_t)u.in_len * 2048)) runs.push_back({s, 0, refs[s].size()});
+            else refs[s].clear();
+        }
+    if (runs.empty()) return run_units(SWC_CODEC_LZMA2, streams);
+    // one list for one launch: the streams that stay whole as they are, every other one as its units -- each with its exact capacity
+    // and its place in the stream's result, so nothing is joined afterwards
+    std::vector<HostUnit> units;
+    std::vector<size_t> whole_at(streams.size(), (size_t)-1);
+    std::vector<std::vector<uint8_t>> joined(runs.size());
+    for (size_t s = 0, r = 0; s < streams.size(); s++) {
+        HostUnit& st = streams[s];
+        if (refs[s].empty()) { whole_at[s] = units.size(); units.push_back(std::move(st)); continue; }
+        size_t total = 0;
+        for (const BlockRef64& f : refs[s]) total += (size_t)f.uncomp_len;
+        uint8_t* place = st.dst;
+        if (!place || st.dst_cap < total) { joined[r].resize(total); place = joined[r].data(); }
+        runs[r++].first = units.size();
+        size_t at = 0;
+        for (const BlockRef64& f : refs[s]) {
+            HostUnit u;
+            u.in = st.in + f.offset;
+            u.in_len = (size_t)f.comp_len;
+            u.base = st.base ? st.base : st.in;                 // the stream is staged once, every unit a sub-range of it
+            u.base_len = st.base ? st.base_len : st.in_len;
+            u.aux = (int32_t)f.aux;
+            u.cap_hint = (size_t)f.uncomp_len;
+            u.cap_exact = true;
+            u.dst = place + at;
+            u.dst_cap = (size_t)f.uncomp_len;
+            u.sum_kind = st.sum_kind == SWC_SUM_CRC32 ? st.sum_kind : 0;   // (CRC-32 combines; any other check is taken over the joined block, on the host)
+            at += (size_t)f.uncomp_len;
+            units.push_back(std::move(u));
+        }
+    }
+    int rc = run_units(SWC_CODEC_LZMA2, units);
+    if (rc != SWC_OK) return rc;
+    for (size_t s = 0; s < streams.size(); s++) if (whole_at[s] != (size_t)-1) streams[s] = std::move(units[whole_at[s]]);
+    std::vector<size_t> fallback;
+    for (size_t r = 0; r < runs.size(); r++) {
+        const Run& run = runs[r];
+        HostUnit& st = streams[run.stream];
+        const std::vector<BlockRef64>& f = refs[run.stream];
+        bool ok = true;
+        for (size_t k = 0; k + 1 < run.count && ok; k++) {
+            const HostUnit& u = units[run.first + k];
+            ok = u.status == SWC_OK && (u.aux_out & SWC_LZMA2_OPEN) != 0 && u.in_consumed == u.in_len && u.in_dst && u.out_size == f[k].uncomp_len;
+        }
+        const HostUnit& last = units[run.first + run.count - 1];
+        ok = ok && last.status == SWC_OK && last.in_dst;
+        if (!ok) { fallback.push_back(run.stream); continue; }
+        const size_t total = (size_t)(last.dst - units[run.first].dst) + last.out_size;
+        st.status = SWC_OK;
+        st.in_consumed = (size_t)(last.in - st.in) + last.in_consumed;
+        st.aux_out = 0;
+        st.out_size = total;
+        st.in_dst = joined[r].empty() && total != 0;
+        if (st.in_dst) st.out.clear();
+        else { joined[r].resize(total); st.out = std::move(joined[r]); }
+        st.sum_valid = false;
+        if (st.sum_kind == SWC_SUM_CRC32) {   // the units' sums, combined: no pass over the joined output
+            bool valid = true;
+            uint32_t sum = 0;
+            for (size_t k = 0; k < run.count && valid; k++) {
+                const HostUnit& u = units[run.first + k];
+                valid = u.sum_valid;
+                sum = swc_crc32_combine(sum, (uint32_t)u.sum, u.out_size);
+            }
+            st.sum = sum;
+            st.sum_valid = valid;
+        }
+        stat_add(5, (long long)run.count);
+    }
+    if (!fallback.empty()) {   // as ever, and that result is the stream's
+        std::vector<HostUnit> whole(fallback.size());
+        for (size_t i = 0; i < fallback.size(); i++) whole[i] = std::move(streams[fallback[i]]);
+        stat_add(6, (long long)fallback.size());
+        rc = run_units(SWC_CODEC_LZMA2, whole);
+        for (size_t i = 0; i < fallback.size(); i++) streams[fallback[i]] = std::move(whole[i]);
+        if (rc != SWC_OK) return rc;
+    }
+    return SWC_OK;
+}
+int run_lzma2_one(HostUnit& u) {
+    std::vector<HostUnit> v(1);
+    v[0] = std::move(u);
+    int st = run_lzma2(v);
+    u = std::move(v[0]);
+    return st;
 }
 
 }  // namespace swc
@@ -591,7 +745,7 @@ int swc_lzma2_decompress(const uint8_t* in, size_t in_len, uint8_t dict_byte, ui
     u.aux = dict_byte;
     u.cap_hint = lzma2_announced_size(in, in_len);
     if (u.cap_hint == 0) u.cap_hint = 16;
-    int st = run_one(SWC_CODEC_LZMA2, u);
+    int st = run_lzma2_one(u);
     if (st) { give_empty(out, out_len); return st; }
     if (in_consumed) *in_consumed = u.in_consumed;
     if (u.status) { give_empty(out, out_len); return u.status; }

@@ -63,7 +63,7 @@ int many_single_unit(int kind, const uint8_t* const* archives, const size_t* len
         data_pos.push_back(p);
     }
     if (!units.empty()) {
-        int st = codec == SWC_CODEC_DEFLATE ? run_deflate(units) : run_units(codec, units);   // (flushed streams as runs of units, in the same launch)
+        int st = codec == SWC_CODEC_DEFLATE ? run_deflate(units) : run_lzma2(units);   // (flushed streams, and streams with dictionary resets, as runs of units in the same launch)
         if (st) return st;
     }
     for (size_t k = 0; k < units.size(); k++) {
@@ -469,6 +469,7 @@ int swc_index_blocks(int kind, const uint8_t* in, size_t len, swc_block_ref* ref
         case 5: bzip2_magic_index(in, len, v); break;
         case 6: xz_block_index(in, len, v); break;
         case 7: st = lzma2_chunk_index(in, len, v); break;
+        case 8: lzma2_unit_index(in, len, 1, len ? in[0] : (uint8_t)0, lzma2_run_bytes(), v); break;
         default: return SWC_E_INVALID_ARGUMENT;
     }
     if (!ok) { *n = 0; return SWC_E_INVALID_ARGUMENT; }
@@ -539,7 +540,7 @@ int swc_7z_unpack_folders(swc_7z_folder* folders, size_t n) try {
                     u.dict_value = (uint64_t)c.props[1] | (uint64_t)c.props[2] << 8 | (uint64_t)c.props[3] << 16 | (uint64_t)c.props[4] << 24;
                 }
             }
-            if (run_units(m == 1 ? SWC_CODEC_DEFLATE : m == 3 ? SWC_CODEC_LZMA2 : SWC_CODEC_LZMA, units) != SWC_OK) return SWC_E_DEVICE;
+            if ((m == 3 ? run_lzma2(units) : run_units(m == 1 ? SWC_CODEC_DEFLATE : SWC_CODEC_LZMA, units)) != SWC_OK) return SWC_E_DEVICE;
             for (size_t k = 0; k < idx.size(); k++) {
                 next[idx[k]].status = units[k].status;
                 if (!units[k].status) next[idx[k]].data = std::move(units[k].out);

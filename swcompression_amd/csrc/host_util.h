@@ -101,7 +101,7 @@ struct HostUnit {
     size_t size() const { return in_dst ? out_size : out.size(); }
     size_t in_consumed = 0;
     int32_t status = SWC_OK;
-    int32_t aux_out = 0;         // codec specific result (bzip2: computed block CRC; Deflate: SWC_DEFLATE_OPEN where the unit ended open)
+    int32_t aux_out = 0;         // codec specific result (bzip2: computed block CRC; Deflate: SWC_DEFLATE_OPEN, LZMA2: SWC_LZMA2_OPEN where the unit ended open)
     // results of a Deflate run, on its head: the units in front of unit run_used ended open at their last byte; run_ok: unit run_used
     // met a final block, and the head's output is the stream's -- run_bytes of it (out_size stays the head's own share)
     bool run_ok = false;
@@ -127,7 +127,7 @@ struct Trace {
 };
 
 // swc_stat counters (api.cpp)
-void stat_add(int which, long long v);   // 0 launches, 1 units, 2 xz_cache_hits, 3 deflate_unit_fallbacks, 4 sha256_device_units
+void stat_add(int which, long long v);   // 0 launches, 1 units, 2 xz_cache_hits, 3 deflate_unit_fallbacks, 4 sha256_device_units, 5 lzma2_run_units, 6 lzma2_run_fallbacks
 
 }  // namespace swc
 #endif

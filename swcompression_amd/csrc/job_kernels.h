@@ -285,7 +285,11 @@ SWC_D void lzma_stream(Job* __restrict__ jobs, uint32_t g, uint8_t* spill, uint1
     Job job = jobs[g];
     SWC_AS_GLOBAL uint16_t* sp = spill ? (SWC_AS_GLOBAL uint16_t*)(spill + (size_t)g * kLzmaSpillBytes) : nullptr;
     lzma::lzma_job<WAVE>(job, LZMA2, lds, sp, lane, LDSBITS < 0 ? 0 : LDSBITS, prof_of(prof, g, 0), LDSBITS < 0);
-    if (lane == 0) put_result(jobs, g, job);
+    if (lane == 0) {
+        // (aux: SWC_LZMA2_OPEN is an OUT bit.  Read again from the record, so that the decode keeps nothing of it but the dictionary byte)
+        if (LZMA2) job.aux = lzma::lzma2_end(job, *(const volatile int32_t*)&jobs[g].aux);
+        put_result<LZMA2>(jobs, g, job);
+    }
 }
 
 // ---- BZip2 --------------------------------------------------------------------------------------------------------------------

@@ -613,6 +613,13 @@ struct Decoder {
     }
 
     // LZMA2Decoder.init + decode(): Sources/LZMA2/LZMA2Decoder.swift:17-99
+    // kEndAtControl: the reader stood exactly at the end of the input when the chunk loop went to read a control byte -- at the top
+    // of the loop nothing past the end has been read yet (decode() and the stored copy return an error otherwise), so the trap
+    // behind that read means just this.  The reference's trap for any job but an open unit (lzma2_end: SWC_LZMA2_OPEN); said by the
+    // value returned, so that nothing about it is kept across decode() -- not even the job's aux, which lzma2_end reads again from
+    // the record.  No byte at or behind in + n is ever loaded (win_load, the stored copy): bytes past the end read as zero from
+    // the register window.
+    static constexpr int kEndAtControl = -1;
     SWC_HD int decode_lzma2(uint8_t dict_byte) {
         if (same(dict_byte & 0xC0)) return SWC_E_LZMA2_WRONG_DICTIONARY_SIZE;  // :21
         const int bits = dict_byte & 0x3F;
@@ -622,7 +629,7 @@ struct Decoder {
         for (;;) {
             ensure_window();
             const uint32_t control = next_byte();                        // :36
-            if (same(trapped())) return SWC_E_REF_TRAP;
+            if (same(trapped())) return kEndAtControl;
             if (same(control == 0)) return SWC_OK;
             if (same(control == 1 || control == 2)) {
                 if (same(control == 1)) reset_dictionary();
@@ -668,7 +675,7 @@ struct Decoder {
     }
 };
 
-// job.aux: LZMA2 = dictionary-size byte; LZMA = lc | lp << 8 | pb << 16.
+// job.aux: LZMA2 = dictionary-size byte | SWC_LZMA2_OPEN (an OUT bit: it stays where the unit ended open); LZMA = lc | lp << 8 | pb << 16.
 // job.dict_len: LZMA = declared uncompressed size (UINT64_MAX = unknown); job.dict (reinterpreted) = dictionary size.
 template <int WAVE>
 SWC_HD void lzma_job(Job& job, bool is_lzma2, uint16_t* probs, SWC_AS_GLOBAL uint16_t* lit_spill, int lane, int lds_bits = kMaxLdsLitBits, uint64_t* prof = nullptr, bool cached = false) {
@@ -691,7 +698,7 @@ SWC_HD void lzma_job(Job& job, bool is_lzma2, uint16_t* probs, SWC_AS_GLOBAL uin
     d.win_load(0);
     int st;
     if (is_lzma2) {
-        st = d.decode_lzma2((uint8_t)job.aux);
+        st = d.decode_lzma2((uint8_t)job.aux);   // (kEndAtControl goes out as it is: lzma2_end below, by whoever holds the job record)
     } else {
         d.lc = job.aux & 0xFF; d.lp = (job.aux >> 8) & 0xFF; d.pb = (job.aux >> 16) & 0xFF;
         d.dict_size = (uint64_t)(uintptr_t)job.dict;
@@ -711,6 +718,16 @@ SWC_HD void lzma_job(Job& job, bool is_lzma2, uint16_t* probs, SWC_AS_GLOBAL uin
 #else
     (void)prof;
 #endif
+}
+
+// What lzma_job left of an LZMA2 job, against `aux` as the job record holds it: an open unit (SWC_LZMA2_OPEN, include/swc_hip.h) that
+// stood exactly at the end of its input when the next control byte was due ended well, for any other job that is the reference's
+// trap.  Returns the aux to write back: the bit stays only where the unit ended open -- and where the job has to come back with a
+// workspace, its list unchanged.
+SWC_HD int32_t lzma2_end(Job& job, int32_t aux) {
+    const bool ended_open = job.status == Decoder<1>::kEndAtControl && (aux & kLzma2Open) != 0 && job.in_consumed != 0;   // (there in_consumed is in_len; in_len = 0 keeps its status)
+    if (job.status == Decoder<1>::kEndAtControl) job.status = ended_open ? (int32_t)SWC_OK : (int32_t)SWC_E_REF_TRAP;
+    return ended_open || job.status == SWC_E_NEED_WORKSPACE ? aux : aux & ~kLzma2Open;
 }
 
 }  // namespace lzma

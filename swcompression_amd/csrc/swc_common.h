@@ -54,6 +54,8 @@ struct Job {
 constexpr int32_t kLz4Linked = 1, kLz4Stored = 2;
 // aux of a Deflate job (include/swc_hip.h: SWC_DEFLATE_JOINED, SWC_DEFLATE_OPEN, SWC_DEFLATE_LINKED)
 constexpr int32_t kDeflateJoined = 1, kDeflateOpen = 2, kDeflateLinked = 4;
+// aux of an LZMA2 job above its dictionary-size byte (include/swc_hip.h: SWC_LZMA2_OPEN)
+constexpr int32_t kLzma2Open = 0x100;
 
 // A kernel's results back to its entry of the job list (AUX: `aux` too -- bzip2's block CRC)
 template <bool AUX = false>
