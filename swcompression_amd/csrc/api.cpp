@@ -154,8 +154,8 @@ void host_result_free(void* p) {
     free(p);
 }
 
-static std::atomic<long long> g_stats[7];
-void stat_add(int which, long long v) { if (which >= 0 && which < 7) g_stats[which] += v; }
+static std::atomic<long long> g_stats[kStatCount];
+void stat_add(Stat which, long long v) { g_stats[which] += v; }
 
 // What a thread keeps page-locked between calls, per direction.  Pinning is the expensive part of a large single-shot call
 // (a 268 MB result: tens of milliseconds to lock against 5 ms to copy), so a buffer that served an archive of a gigabyte
@@ -221,7 +221,6 @@ static void copy_out(std::vector<CopyOut>& v) {
     for (auto& x : th) x.join();
 }
 
-constexpr int kSumSha256 = 6;   // HostUnit::sum_kind: SHA-256 (host_util.h)
 static int run_units_impl(int codec, std::vector<HostUnit>& units);
 int run_units(int codec, std::vector<HostUnit>& units) {
     const int st = run_units_impl(codec, units);
@@ -382,8 +381,8 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
                 if (launch_sha256(reinterpret_cast<const Job*>(d_jobs), m, d_sums, stream) != hipSuccess) return SWC_E_DEVICE;
             } else if (sum_kind && launch_checksum(sum_kind, reinterpret_cast<const Job*>(d_jobs), m, reinterpret_cast<uint64_t*>(d_sums), stream) != hipSuccess) return SWC_E_DEVICE;
         }
-        stat_add(0, 1);
-        stat_add(1, (long long)m);
+        stat_add(kStatLaunches, 1);
+        stat_add(kStatUnits, (long long)m);
         // device -> host: the job records (they say how much of every output exists), the checksums, the outputs
         std::vector<uint8_t> down_fallback;
         uint8_t* down = pinned_stage(1, down_bytes);
@@ -544,13 +543,13 @@ int swc_set_profile_buffer(void* device_ptr) { set_profile_buffer(device_ptr); r
 
 long long swc_stat(const char* key) {
     if (!key) return -1;
-    if (!strcmp(key, "launches")) return g_stats[0].load();
-    if (!strcmp(key, "units")) return g_stats[1].load();
-    if (!strcmp(key, "xz_cache_hits")) return g_stats[2].load();
-    if (!strcmp(key, "deflate_unit_fallbacks")) return g_stats[3].load();
-    if (!strcmp(key, "sha256_device_units")) return g_stats[4].load();
-    if (!strcmp(key, "lzma2_run_units")) return g_stats[5].load();
-    if (!strcmp(key, "lzma2_run_fallbacks")) return g_stats[6].load();
+    if (!strcmp(key, "launches")) return g_stats[kStatLaunches].load();
+    if (!strcmp(key, "units")) return g_stats[kStatUnits].load();
+    if (!strcmp(key, "xz_cache_hits")) return g_stats[kStatXzCacheHits].load();
+    if (!strcmp(key, "deflate_unit_fallbacks")) return g_stats[kStatDeflateUnitFallbacks].load();
+    if (!strcmp(key, "sha256_device_units")) return g_stats[kStatSha256DeviceUnits].load();
+    if (!strcmp(key, "lzma2_run_units")) return g_stats[kStatLzma2RunUnits].load();
+    if (!strcmp(key, "lzma2_run_fallbacks")) return g_stats[kStatLzma2RunFallbacks].load();
     return -1;
 }
 

@@ -239,7 +239,7 @@ int swc_bzip2_compress(const uint8_t* data, size_t len, int block_size, uint8_t*
     if (!device_ready()) { give_empty(out, out_len); return SWC_E_DEVICE; }
     const int st = bzip2_compress_device(data, len, block_size, out, out_len);   // assembled in the caller's buffer
     if (st) { give_empty(out, out_len); return st; }
-    stat_add(0, 1);
+    stat_add(kStatLaunches, 1);
     return SWC_OK;
 } catch (...) {
     if (out && out_len) give_empty(out, out_len);

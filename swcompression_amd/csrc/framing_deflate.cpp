@@ -18,37 +18,13 @@
 
 namespace swc {
 
-int run_one(int codec, HostUnit& u) {
-    std::vector<HostUnit> v(1);
-    v[0] = std::move(u);
-    int st = run_units(codec, v);
-    u = std::move(v[0]);
-    return st;
-}
-
-// run_one for a unit that is followed by unrelated data (the next members of a file, the next entries of a container):
-// first with only `bound` bytes of input staged; the result stands if the unit decoded cleanly and ended inside them,
-// anything else is decided by a second run over the whole tail -- so that a walk over M units stages O(file) bytes, not
-// M times the rest of the file, and the outcome is the one the reference (which reads on from one reader) would have.
-int run_one_bounded(int codec, HostUnit& u, size_t bound) {
-    if (u.in_len <= bound) return run_one(codec, u);
-    HostUnit t = u;
-    t.in_len = bound;
-    int st = run_one(codec, t);
-    if (st != SWC_OK) return st;
-    if (t.status == SWC_OK && t.in_consumed + 64 <= bound) { u = std::move(t); return SWC_OK; }
-    return run_one(codec, u);
-}
-
 // ---- streams cut at their flush points ----------------------------------------------------------------------------------------
 // An empty stored block -- what Z_FULL_FLUSH / Z_SYNC_FLUSH, pigz and this library's own segmented encoder (kCompressSegment below)
 // put between the pieces of a stream -- ends with 00 00 FF FF on a byte boundary, and the next block starts on the next byte.  So a
 // stream is CUT behind every such marker into units that decode in parallel (include/swc_hip.h: SWC_DEFLATE_OPEN,
 // SWC_DEFLATE_JOINED), as long as no unit refers to bytes in front of itself.  The marker is only a guess -- the four bytes occur in
-// stored data and in codes too -- and the guess is checked by the decode itself: the result of the units stands only if every unit
-// in front of some unit k ended open exactly at its last byte with SWC_OK and unit k met a final block with SWC_OK; by induction
-// that is what the sequential parse does.  Anything else -- a false marker, a unit that reaches back (Z_SYNC_FLUSH), any error -- and
-// the stream is decoded whole, as ever, and THAT result is reported.
+// stored data and in codes too -- which the decode checks (framing_runs.cpp: the verdict and the fallback); here the unit that ends
+// the stream is the first that met a final block, and a unit that reaches back (Z_SYNC_FLUSH) fails in its unit.
 // "deflate_units_linked" = 1: every unit but the first is SWC_DEFLATE_LINKED as well -- it shares the history of the units in front of
 // it, which one wave copies as a chain (deflate_chain.h) -- so a unit that reaches back is no reason to fall back any more: default
 // pigz and Z_SYNC_FLUSH streams decode as units.  The verdict is the same rule; a false marker or a broken stream still falls back.
@@ -84,125 +60,46 @@ void deflate_unit_index(const uint8_t* in, size_t len, size_t unit_bytes, std::v
     out.push_back({start, len - start, 0, out.empty() ? 0u : behind});
 }
 
-int run_deflate(std::vector<HostUnit>& streams) {
-    const size_t ub = g_deflate_unit_bytes.load();
-    struct Run { size_t stream, first, count; };
-    std::vector<Run> runs;
-    std::vector<std::vector<BlockRef64>> refs(streams.size());
-    if (ub != 0)
-        for (size_t s = 0; s < streams.size(); s++) {
-            const HostUnit& u = streams[s];
-            if (u.in_len > ub && !u.dict && !u.chain && u.aux == 0) deflate_unit_index(u.in, u.in_len, ub, refs[s]);
-            if (refs[s].size() >= 2) runs.push_back({s, 0, refs[s].size()});
-        }
-    if (runs.empty()) return run_units(SWC_CODEC_DEFLATE, streams);
-    // one list for one launch: the streams that stay whole as they are, every other one as its run
-    std::vector<HostUnit> units;
-    std::vector<size_t> whole_at(streams.size(), (size_t)-1);
-    {
-        size_t r = 0;
-        for (size_t s = 0; s < streams.size(); s++) {
-            HostUnit& st = streams[s];
-            if (refs[s].size() < 2) { whole_at[s] = units.size(); units.push_back(std::move(st)); continue; }
-            runs[r++].first = units.size();
-            for (size_t k = 0; k < refs[s].size(); k++) {
-                HostUnit u;
-                u.in = st.in + refs[s][k].offset;
-                u.in_len = (size_t)refs[s][k].comp_len;
-                u.base = st.base ? st.base : st.in;                 // the stream is staged once, every unit a sub-range of it
-                u.base_len = st.base ? st.base_len : st.in_len;
-                u.aux = (int32_t)refs[s][k].aux;
-                u.chain = true;
-                u.sum_kind = st.sum_kind;
-                // room: six times the compressed size (the static blocks of this library's own encoder pack text 4.2 : 1; the runner's
-                // four would send every such unit round again), never more than the whole stream is said to hold; a unit that needs
-                // more says how much, and the run goes once more with exactly that
-                u.cap_hint = std::max<size_t>(65536, u.in_len * 6 + 1024);
-                if (st.cap_hint) u.cap_hint = std::min(u.cap_hint, std::max<size_t>(st.cap_hint, 64));
-                if (k == 0) { u.run_len = refs[s].size(); u.dst = st.dst; u.dst_cap = st.dst_cap; }
-                units.push_back(std::move(u));
-            }
-        }
-    }
-    int rc = run_units(SWC_CODEC_DEFLATE, units);
-    if (rc != SWC_OK) return rc;
-    // a run that lacked room: every unit has reported its exact size (phase 1 counts on past the capacity) -- once more with those
-    {
-        std::vector<HostUnit> again;
-        std::vector<size_t> which;
-        for (size_t r = 0; r < runs.size(); r++) {
-            const HostUnit& h = units[runs[r].first];
-            if (h.run_ok || units[runs[r].first + h.run_used].status != SWC_E_CAPACITY) continue;
-            which.push_back(r);
-            for (size_t k = 0; k < runs[r].count; k++) {
-                const HostUnit& o = units[runs[r].first + k];
-                HostUnit u;
-                u.in = o.in; u.in_len = o.in_len; u.base = o.base; u.base_len = o.base_len; u.aux = o.aux; u.chain = true;
-                u.sum_kind = o.sum_kind; u.run_len = o.run_len; u.dst = o.dst; u.dst_cap = o.dst_cap;
-                u.cap_hint = (size_t)std::max<uint64_t>(std::min<uint64_t>(o.need, (uint64_t)o.in_len * 1032 + 64), 64);
-                u.cap_exact = true;
-                again.push_back(std::move(u));
-            }
-        }
-        if (!again.empty()) {
-            rc = run_units(SWC_CODEC_DEFLATE, again);
-            if (rc != SWC_OK) return rc;
-            size_t at = 0;
-            for (size_t r : which)
-                for (size_t k = 0; k < runs[r].count; k++) units[runs[r].first + k] = std::move(again[at++]);
-        }
-    }
-    for (size_t s = 0; s < streams.size(); s++) if (whole_at[s] != (size_t)-1) streams[s] = std::move(units[whole_at[s]]);
-    std::vector<size_t> fallback;
-    for (const Run& r : runs) {
-        HostUnit& st = streams[r.stream];
-        HostUnit& h = units[r.first];
-        if (!h.run_ok) { fallback.push_back(r.stream); continue; }
-        const HostUnit& last = units[r.first + h.run_used];
-        st.status = SWC_OK;
-        st.in_consumed = (size_t)(last.in - st.in) + last.in_consumed;
-        st.out = std::move(h.out);
-        st.in_dst = h.in_dst;
-        st.out_size = h.run_bytes;
-        st.aux_out = 0;
-        if (st.sum_kind == SWC_SUM_CRC32 || st.sum_kind == SWC_SUM_ADLER32) {   // the units' sums, combined: no pass over the joined output
-            bool valid = true;
-            uint32_t sum = st.sum_kind == SWC_SUM_CRC32 ? 0u : 1u;
-            for (size_t k = 0; k <= h.run_used && valid; k++) {
-                const HostUnit& u = units[r.first + k];
-                valid = u.sum_valid;
-                sum = st.sum_kind == SWC_SUM_CRC32 ? swc_crc32_combine(sum, (uint32_t)u.sum, u.out_size) : swc_adler32_combine(sum, (uint32_t)u.sum, u.out_size);
-            }
-            st.sum = sum;
-            st.sum_valid = valid;
-        }
-    }
-    if (!fallback.empty()) {   // as ever, and that result is the stream's
-        std::vector<HostUnit> whole(fallback.size());
-        for (size_t i = 0; i < fallback.size(); i++) whole[i] = std::move(streams[fallback[i]]);
-        stat_add(3, (long long)fallback.size());
-        rc = run_units(SWC_CODEC_DEFLATE, whole);
-        for (size_t i = 0; i < fallback.size(); i++) streams[fallback[i]] = std::move(whole[i]);
-        if (rc != SWC_OK) return rc;
-    }
-    return SWC_OK;
+// What Deflate adds to run_streams (framing.h: RunCodec).  The units of a run are a chain: the runner lays their outputs out back to
+// back, copies the run out once as its head's output and leaves the verdict on the head (run_ok, run_used, run_bytes).
+static void deflate_run_index(const HostUnit& st, size_t unit_bytes, std::vector<BlockRef64>& refs) {
+    if (st.aux == 0) deflate_unit_index(st.in, st.in_len, unit_bytes, refs);
 }
-int run_deflate_one(HostUnit& u) {
-    std::vector<HostUnit> v(1);
-    v[0] = std::move(u);
-    int st = run_deflate(v);
-    u = std::move(v[0]);
-    return st;
+static void deflate_run_fill(const HostUnit& st, const std::vector<BlockRef64>& refs, HostUnit* run, const HostUnit* again, std::vector<uint8_t>&) {
+    for (size_t k = 0; k < refs.size(); k++) {
+        HostUnit& u = run[k];
+        u.chain = true;
+        u.sum_kind = st.sum_kind;
+        if (again) {   // every unit has reported its exact size (phase 1 counts on past the capacity): once more with those
+            u.cap_hint = (size_t)std::max<uint64_t>(std::min<uint64_t>(again[k].need, (uint64_t)u.in_len * 1032 + 64), 64);
+            u.cap_exact = true;
+            continue;
+        }
+        // room: six times the compressed size (the static blocks of this library's own encoder pack text 4.2 : 1; the runner's
+        // four would send every such unit round again), never more than the whole stream is said to hold; a unit that needs
+        // more says how much, and the run goes once more with exactly that
+        u.cap_hint = std::max<size_t>(65536, u.in_len * 6 + 1024);
+        if (st.cap_hint) u.cap_hint = std::min(u.cap_hint, std::max<size_t>(st.cap_hint, 64));
+    }
+    run[0].run_len = refs.size();
+    run[0].dst = st.dst;
+    run[0].dst_cap = st.dst_cap;
 }
-// run_one_bounded for a Deflate stream
-int run_deflate_one_bounded(HostUnit& u, size_t bound) {
-    if (u.in_len <= bound) return run_deflate_one(u);
-    HostUnit t = u;
-    t.in_len = bound;
-    int st = run_deflate_one(t);
-    if (st != SWC_OK) return st;
-    if (t.status == SWC_OK && t.in_consumed + 64 <= bound) { u = std::move(t); return SWC_OK; }
-    return run_deflate_one(u);
+static bool deflate_run_lacked_room(const HostUnit* run) {   // (run_used == run_len: every unit ended open, none lacked room)
+    return !run[0].run_ok && run[0].run_used < run[0].run_len && run[run[0].run_used].status == SWC_E_CAPACITY;
+}
+static bool deflate_run_verdict(HostUnit& st, const std::vector<BlockRef64>&, HostUnit* run, std::vector<uint8_t>&, size_t& last) {
+    if (!run[0].run_ok) return false;
+    last = run[0].run_used;
+    st.out = std::move(run[0].out);
+    st.in_dst = run[0].in_dst;
+    st.out_size = run[0].run_bytes;
+    return true;
+}
+const RunCodec& deflate_runs() {
+    static const RunCodec c = {SWC_CODEC_DEFLATE, kStatDeflateUnitFallbacks, 1u << SWC_SUM_CRC32 | 1u << SWC_SUM_ADLER32, deflate_unit_bytes,
+                               deflate_run_index, deflate_run_fill, deflate_run_lacked_room, deflate_run_verdict};
+    return c;
 }
 
 void give(const std::vector<uint8_t>& src, uint8_t** out, size_t* out_len) {
@@ -349,7 +246,7 @@ int swc_deflate_decompress(const uint8_t* in, size_t in_len, uint8_t** out, size
     if (!out || !out_len || (in_len && !in)) return SWC_E_INVALID_ARGUMENT;
     HostUnit u;
     u.in = in; u.in_len = in_len;
-    int st = run_deflate_one(u);
+    int st = run_one(SWC_CODEC_DEFLATE, u, kCut);
     if (st) { give_empty(out, out_len); return st; }
     if (in_consumed) *in_consumed = u.in_consumed;
     if (u.status) { give_empty(out, out_len); return u.status; }       // DeflateError cases carry no data
@@ -367,7 +264,7 @@ int swc_gzip_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, size_t* 
     if (st) { give_empty(out, out_len); return st; }
     const size_t data_pos = (size_t)(u.in - in);
     u.sum_kind = 1;                                                    // CRC-32 on the device, behind the decode
-    st = run_deflate_one(u);
+    st = run_one(SWC_CODEC_DEFLATE, u, kCut);
     if (st) { give_empty(out, out_len); return st; }
     size_t next; bool crc_error;
     st = gzip_member_finish(in, in_len, data_pos, u, next, crc_error);
@@ -478,7 +375,7 @@ int swc_gzip_multi_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, si
         if (st) break;
         u.cap_hint = 0;                                                // ISIZE guess only valid for the last member
         const size_t data_pos = (size_t)(u.in - in);
-        st = run_deflate_one_bounded(u, walk_bound);
+        st = run_one_bounded(SWC_CODEC_DEFLATE, u, walk_bound, kCut);
         if (st) break;
         walk_bound = std::max<size_t>(walk_bound, 4 * u.in_consumed + 65536);   // the next member is probably of this size
         bool crc_error;
@@ -746,8 +643,8 @@ int swc_bgzf_archive(const uint8_t* data, size_t len, size_t block_size, int dyn
         for (size_t k = 0; k < cnt; k++) msz.push_back((size_t)round_sizes[k]);
         pos += (size_t)total;
         done += m;
-        stat_add(0, 1);
-        stat_add(1, (long long)m);
+        stat_add(kStatLaunches, 1);
+        stat_add(kStatUnits, (long long)m);
     } while (done < n);
     if (st != SWC_OK) { host_result_free(res); give_empty(out, out_len); return st; }
     *out = res;
@@ -768,7 +665,7 @@ int swc_zlib_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, size_t* 
     HostUnit u;
     u.in = in + p; u.in_len = in_len - p;
     u.sum_kind = 2;                                                    // Adler-32 on the device, behind the decode
-    st = run_deflate_one(u);
+    st = run_one(SWC_CODEC_DEFLATE, u, kCut);
     if (st) { give_empty(out, out_len); return st; }
     if (u.status) { give_empty(out, out_len); return u.status; }
     size_t q = p + u.in_consumed;

@@ -86,12 +86,6 @@ size_t lzma2_announced_size(const uint8_t* p, size_t n) {
 
 namespace {
 
-int run_lzma_unit(int codec, HostUnit& u) {
-    int st = codec == SWC_CODEC_LZMA2 ? run_lzma2_one(u) : run_one(codec, u);
-    if (st) return st;
-    return SWC_OK;
-}
-
 void delta_decode(const std::vector<uint8_t>& in, int distance, std::vector<uint8_t>& out) {  // DeltaFilter.swift:11-33
     uint8_t delta[256] = {0};
     int pos = 0;
@@ -119,7 +113,6 @@ struct Predecoded {
 // what xz_block knows about the data it appended beyond the bytes: a checksum the device computed (a block whose only filter
 // is LZMA2 and whose data were decoded ahead)
 struct BlockSum { int kind = 0; uint64_t sum = 0; uint8_t digest[32] = {0}; };
-constexpr int kSumSha256 = 6;   // HostUnit::sum_kind (host_util.h)
 // "sha256_device_min_units": the fewest units of a run_units call whose SHA-256 checks the device computes.  MEASURED (DESIGN.md
 // 4.3.1, profiles/sha256.txt): a lane hashes 22 MB/s, a host thread 400 MB/s, so the launch needs 32 blocks to be ahead
 std::atomic<int> g_sha256_min_units{32};
@@ -188,7 +181,7 @@ int xz_block(uint32_t header_size_byte, Reader& r, int check_size, std::vector<u
             next = std::move(hit->second.out);
             if (bsum && filters_count == 1) { bsum->kind = hit->second.sum_kind; bsum->sum = hit->second.sum; memcpy(bsum->digest, hit->second.digest, 32); }
             cache->erase(hit);
-            stat_add(2, 1);
+            stat_add(kStatXzCacheHits, 1);
         } else if (filters[i].id == 0x21) {
             HostUnit u;
             u.in = have_cur ? cur.data() : r.d + r.off;
@@ -196,7 +189,7 @@ int xz_block(uint32_t header_size_byte, Reader& r, int check_size, std::vector<u
             u.aux = filters[i].prop;
             u.cap_hint = lzma2_announced_size(u.in, u.in_len);
             if (u.cap_hint == 0) u.cap_hint = 16;
-            if ((st = run_lzma_unit(SWC_CODEC_LZMA2, u))) return st;
+            if ((st = run_one(SWC_CODEC_LZMA2, u, kCut))) return st;
             if (!have_cur) r.off += (int64_t)u.in_consumed;
             if (u.status) return u.status;
             next = std::move(u.out);
@@ -296,7 +289,7 @@ int xz_stream(Reader& r, std::vector<uint8_t>& out, bool& check_error, BlockCach
         } else if (check_type == 0x0A) {
             if (r.left() < 32) return SWC_E_REF_TRAP;
             uint8_t dg[32];
-            if (bsum.kind == kSumSha256) stat_add(4, 1);
+            if (bsum.kind == kSumSha256) stat_add(kStatSha256DeviceUnits, 1);
             else swc_sha256(bd, bl, dg);
             const bool ok = memcmp(bsum.kind == kSumSha256 ? bsum.digest : dg, r.d + r.off, 32) == 0;
             r.off += 32;
@@ -426,7 +419,7 @@ void xz_predecode(const uint8_t* d, size_t n, BlockCache& cache) {
     for (const Cand& c : cands) if (c.check_type != cands[0].check_type) kind = 0;
     std::vector<HostUnit> units;
     xz_units(d, n, cands, kind, cands[0].check_type, units);
-    if (run_lzma2(units) != SWC_OK) return;   // (blocks x runs in the one launch)
+    if (run_streams(SWC_CODEC_LZMA2, units, kCut) != SWC_OK) return;   // (blocks x runs in the one launch)
     xz_cache_fill(cands, units, 0, cache);
 }
 
@@ -494,7 +487,7 @@ int xz_run_many(const uint8_t* const* archives, const size_t* lens, size_t n, st
         first[i] = units.size();
         xz_units(archives[i], lens[i], cands[i], xz_sum_kind(major, total), major, units);
     }
-    if (!units.empty() && run_lzma2(units) != SWC_OK) return SWC_E_DEVICE;
+    if (!units.empty() && run_streams(SWC_CODEC_LZMA2, units, kCut) != SWC_OK) return SWC_E_DEVICE;
     statuses.assign(n, SWC_OK);
     outs.assign(n, std::vector<uint8_t>());
     for (size_t i = 0; i < n; i++) {
@@ -554,9 +547,8 @@ int lzma2_chunk_walk(const uint8_t* in, size_t in_len, size_t p, std::vector<Blo
 // step for step what the stream does.  A stored chunk with control 1 resets the dictionary only: the model goes on behind it unless
 // the next chunk that is not stored resets state and properties (control >= 0xC0) -- only then is it a cut.
 // The cuts are candidates: a match may reach behind a reset (legal in the reference, LZMADecoder.swift:269,297; it fails in a
-// unit, whose checks are at least as strict as the stream's).  The result of the units stands only if every unit but the last
-// ended open exactly at its last byte with SWC_OK and exactly its announced size, and the last is SWC_OK; anything else and the
-// stream is decoded whole, as ever, and THAT result is reported -- error order, error-carried data and the quirks stay exact.
+// unit, whose checks are at least as strict as the stream's), which the decode checks (framing_runs.cpp: the verdict and the
+// fallback); here the unit that ends the stream is the last, and every unit in front must have exactly its announced size too.
 // "lzma2_run_bytes": the least compressed size of a unit, 0 = never cut.  It ships as 0 -- the host paths decode as they always
 // did; flipping it is a follow-up that cites profiles/lzma2_runs.txt (tools/exp_lzma2_runs.py).
 static std::atomic<size_t> g_lzma2_run_bytes{0};
@@ -592,107 +584,50 @@ void lzma2_unit_index(const uint8_t* in, size_t len, size_t first, uint8_t dict_
     out.push_back({unit_start, len - unit_start, announced - unit_p, (uint32_t)dict_byte});
 }
 
-int run_lzma2(std::vector<HostUnit>& streams) {
-    const size_t rb = g_lzma2_run_bytes.load();
-    struct Run { size_t stream, first, count; };
-    std::vector<Run> runs;
-    std::vector<std::vector<BlockRef64>> refs(streams.size());
-    if (rb != 0)
-        for (size_t s = 0; s < streams.size(); s++) {
-            const HostUnit& u = streams[s];
-            if (u.in_len <= rb || u.dict || u.chain || (u.aux & ~0xFF) != 0) continue;
-            lzma2_unit_index(u.in, u.in_len, 0, (uint8_t)u.aux, rb, refs[s]);
-            uint64_t total = 0;
-            for (const BlockRef64& r : refs[s]) total += r.uncomp_len;
-            // (exact capacities are taken as they are: the announced sizes of a damaged stream must not size the launch)
-            if (refs[s].size() >= 2 && total <= std::max<uint64_t>((uint64_t)64 << 20, (uint64_t)u.in_len * 2048)) runs.push_back({s, 0, refs[s].size()});
-            else refs[s].clear();
-        }
-    if (runs.empty()) return run_units(SWC_CODEC_LZMA2, streams);
-    // one list for one launch: the streams that stay whole as they are, every other one as its units -- each with its exact capacity
-    // and its place in the stream's result, so nothing is joined afterwards
-    std::vector<HostUnit> units;
-    std::vector<size_t> whole_at(streams.size(), (size_t)-1);
-    std::vector<std::vector<uint8_t>> joined(runs.size());
-    for (size_t s = 0, r = 0; s < streams.size(); s++) {
-        HostUnit& st = streams[s];
-        if (refs[s].empty()) { whole_at[s] = units.size(); units.push_back(std::move(st)); continue; }
-        size_t total = 0;
-        for (const BlockRef64& f : refs[s]) total += (size_t)f.uncomp_len;
-        uint8_t* place = st.dst;
-        if (!place || st.dst_cap < total) { joined[r].resize(total); place = joined[r].data(); }
-        runs[r++].first = units.size();
-        size_t at = 0;
-        for (const BlockRef64& f : refs[s]) {
-            HostUnit u;
-            u.in = st.in + f.offset;
-            u.in_len = (size_t)f.comp_len;
-            u.base = st.base ? st.base : st.in;                 // the stream is staged once, every unit a sub-range of it
-            u.base_len = st.base ? st.base_len : st.in_len;
-            u.aux = (int32_t)f.aux;
-            u.cap_hint = (size_t)f.uncomp_len;
-            u.cap_exact = true;
-            u.dst = place + at;
-            u.dst_cap = (size_t)f.uncomp_len;
-            u.sum_kind = st.sum_kind == SWC_SUM_CRC32 ? st.sum_kind : 0;   // (CRC-32 combines; any other check is taken over the joined block, on the host)
-            at += (size_t)f.uncomp_len;
-            units.push_back(std::move(u));
-        }
-    }
-    int rc = run_units(SWC_CODEC_LZMA2, units);
-    if (rc != SWC_OK) return rc;
-    for (size_t s = 0; s < streams.size(); s++) if (whole_at[s] != (size_t)-1) streams[s] = std::move(units[whole_at[s]]);
-    std::vector<size_t> fallback;
-    for (size_t r = 0; r < runs.size(); r++) {
-        const Run& run = runs[r];
-        HostUnit& st = streams[run.stream];
-        const std::vector<BlockRef64>& f = refs[run.stream];
-        bool ok = true;
-        for (size_t k = 0; k + 1 < run.count && ok; k++) {
-            const HostUnit& u = units[run.first + k];
-            ok = u.status == SWC_OK && (u.aux_out & SWC_LZMA2_OPEN) != 0 && u.in_consumed == u.in_len && u.in_dst && u.out_size == f[k].uncomp_len;
-        }
-        const HostUnit& last = units[run.first + run.count - 1];
-        ok = ok && last.status == SWC_OK && last.in_dst;
-        if (!ok) { fallback.push_back(run.stream); continue; }
-        const size_t total = (size_t)(last.dst - units[run.first].dst) + last.out_size;
-        st.status = SWC_OK;
-        st.in_consumed = (size_t)(last.in - st.in) + last.in_consumed;
-        st.aux_out = 0;
-        st.out_size = total;
-        st.in_dst = joined[r].empty() && total != 0;
-        if (st.in_dst) st.out.clear();
-        else { joined[r].resize(total); st.out = std::move(joined[r]); }
-        st.sum_valid = false;
-        if (st.sum_kind == SWC_SUM_CRC32) {   // the units' sums, combined: no pass over the joined output
-            bool valid = true;
-            uint32_t sum = 0;
-            for (size_t k = 0; k < run.count && valid; k++) {
-                const HostUnit& u = units[run.first + k];
-                valid = u.sum_valid;
-                sum = swc_crc32_combine(sum, (uint32_t)u.sum, u.out_size);
-            }
-            st.sum = sum;
-            st.sum_valid = valid;
-        }
-        stat_add(5, (long long)run.count);
-    }
-    if (!fallback.empty()) {   // as ever, and that result is the stream's
-        std::vector<HostUnit> whole(fallback.size());
-        for (size_t i = 0; i < fallback.size(); i++) whole[i] = std::move(streams[fallback[i]]);
-        stat_add(6, (long long)fallback.size());
-        rc = run_units(SWC_CODEC_LZMA2, whole);
-        for (size_t i = 0; i < fallback.size(); i++) streams[fallback[i]] = std::move(whole[i]);
-        if (rc != SWC_OK) return rc;
-    }
-    return SWC_OK;
+// What LZMA2 adds to run_streams (framing.h: RunCodec).  The units are no chain -- the runner may still launch one again with a
+// workspace -- and each has its exact capacity and its place in the stream's result, so nothing is joined afterwards.
+static void lzma2_run_index(const HostUnit& st, size_t run_bytes, std::vector<BlockRef64>& refs) {
+    if ((st.aux & ~0xFF) != 0) return;
+    lzma2_unit_index(st.in, st.in_len, 0, (uint8_t)st.aux, run_bytes, refs);
+    uint64_t total = 0;
+    for (const BlockRef64& f : refs) total += f.uncomp_len;
+    // (exact capacities are taken as they are: the announced sizes of a damaged stream must not size the launch)
+    if (total > std::max<uint64_t>((uint64_t)64 << 20, (uint64_t)st.in_len * 2048)) refs.clear();
 }
-int run_lzma2_one(HostUnit& u) {
-    std::vector<HostUnit> v(1);
-    v[0] = std::move(u);
-    int st = run_lzma2(v);
-    u = std::move(v[0]);
-    return st;
+static void lzma2_run_fill(const HostUnit& st, const std::vector<BlockRef64>& refs, HostUnit* run, const HostUnit*, std::vector<uint8_t>& joined) {
+    size_t total = 0;
+    for (const BlockRef64& f : refs) total += (size_t)f.uncomp_len;
+    uint8_t* place = st.dst;
+    if (!place || st.dst_cap < total) { joined.resize(total); place = joined.data(); }
+    for (size_t k = 0; k < refs.size(); k++) {
+        HostUnit& u = run[k];
+        u.cap_hint = u.dst_cap = (size_t)refs[k].uncomp_len;
+        u.cap_exact = true;
+        u.dst = place;
+        u.sum_kind = st.sum_kind == SWC_SUM_CRC32 ? st.sum_kind : 0;   // (CRC-32 combines; any other check is taken over the joined block, on the host)
+        place += u.dst_cap;
+    }
+}
+static bool lzma2_run_verdict(HostUnit& st, const std::vector<BlockRef64>& refs, HostUnit* run, std::vector<uint8_t>& joined, size_t& last) {
+    last = refs.size() - 1;
+    bool ok = run[last].status == SWC_OK && run[last].in_dst;
+    for (size_t k = 0; k < last && ok; k++) {
+        const HostUnit& u = run[k];
+        ok = u.status == SWC_OK && (u.aux_out & SWC_LZMA2_OPEN) != 0 && u.in_consumed == u.in_len && u.in_dst && u.out_size == refs[k].uncomp_len;
+    }
+    if (!ok) return false;
+    const size_t total = (size_t)(run[last].dst - run[0].dst) + run[last].out_size;
+    st.out_size = total;
+    st.in_dst = joined.empty() && total != 0;
+    if (st.in_dst) st.out.clear();
+    else { joined.resize(total); st.out = std::move(joined); }
+    stat_add(kStatLzma2RunUnits, (long long)refs.size());
+    return true;
+}
+const RunCodec& lzma2_runs() {
+    static const RunCodec c = {SWC_CODEC_LZMA2, kStatLzma2RunFallbacks, 1u << SWC_SUM_CRC32, lzma2_run_bytes,
+                               lzma2_run_index, lzma2_run_fill, nullptr, lzma2_run_verdict};
+    return c;
 }
 
 }  // namespace swc
@@ -745,7 +680,7 @@ int swc_lzma2_decompress(const uint8_t* in, size_t in_len, uint8_t dict_byte, ui
     u.aux = dict_byte;
     u.cap_hint = lzma2_announced_size(in, in_len);
     if (u.cap_hint == 0) u.cap_hint = 16;
-    int st = run_lzma2_one(u);
+    int st = run_one(SWC_CODEC_LZMA2, u, kCut);
     if (st) { give_empty(out, out_len); return st; }
     if (in_consumed) *in_consumed = u.in_consumed;
     if (u.status) { give_empty(out, out_len); return u.status; }

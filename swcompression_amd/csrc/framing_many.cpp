@@ -63,7 +63,7 @@ int many_single_unit(int kind, const uint8_t* const* archives, const size_t* len
         data_pos.push_back(p);
     }
     if (!units.empty()) {
-        int st = codec == SWC_CODEC_DEFLATE ? run_deflate(units) : run_lzma2(units);   // (flushed streams, and streams with dictionary resets, as runs of units in the same launch)
+        int st = run_streams(codec, units, kCut);   // (flushed streams, and streams with dictionary resets, as runs of units in the same launch)
         if (st) return st;
     }
     for (size_t k = 0; k < units.size(); k++) {
@@ -540,7 +540,8 @@ int swc_7z_unpack_folders(swc_7z_folder* folders, size_t n) try {
                     u.dict_value = (uint64_t)c.props[1] | (uint64_t)c.props[2] << 8 | (uint64_t)c.props[3] << 16 | (uint64_t)c.props[4] << 24;
                 }
             }
-            if ((m == 3 ? run_lzma2(units) : run_units(m == 1 ? SWC_CODEC_DEFLATE : SWC_CODEC_LZMA, units)) != SWC_OK) return SWC_E_DEVICE;
+            const int codec = m == 1 ? SWC_CODEC_DEFLATE : m == 3 ? SWC_CODEC_LZMA2 : SWC_CODEC_LZMA;
+            if (run_streams(codec, units, m == 3 ? kCut : kWhole) != SWC_OK) return SWC_E_DEVICE;   // (only LZMA2 folders are cut)
             for (size_t k = 0; k < idx.size(); k++) {
                 next[idx[k]].status = units[k].status;
                 if (!units[k].status) next[idx[k]].data = std::move(units[k].out);

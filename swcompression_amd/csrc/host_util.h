@@ -58,6 +58,8 @@ void host_result_free(void* p);
 bool device_is_gfx950(int dev);  // api.cpp: device `dev` exists and is a gfx950 (also prepares its memory pool, once)
 bool device_ready();  // api.cpp: true when a gfx950 device is present and selected
 
+constexpr int kSumSha256 = 6;   // HostUnit::sum_kind: SHA-256 (behind the swc_checksum kinds)
+
 // One unit of work for the host-side batch runner (host pointers; the runner stages to HBM).
 struct HostUnit {
     const uint8_t* in = nullptr;
@@ -87,8 +89,8 @@ struct HostUnit {
     uint8_t* dst = nullptr;
     size_t dst_cap = 0;
     // Optional: a checksum of the output computed ON THE DEVICE in the same launch sequence (swc_checksum kinds of
-    // include/swc_hip.h: 1 CRC-32, 2 Adler-32, 3 CRC-64, 4 bzip2 CRC-32, 5 XXH32; 6, internal: SHA-256, swc_batch_sha256's kernel);
-    // one kind per run_units call.
+    // include/swc_hip.h: 1 CRC-32, 2 Adler-32, 3 CRC-64, 4 bzip2 CRC-32, 5 XXH32; kSumSha256, internal: SHA-256, swc_batch_sha256's
+    // kernel); one kind per run_units call.
     int sum_kind = 0;
     // results
     std::vector<uint8_t> out;
@@ -126,8 +128,10 @@ struct Trace {
     }
 };
 
-// swc_stat counters (api.cpp)
-void stat_add(int which, long long v);   // 0 launches, 1 units, 2 xz_cache_hits, 3 deflate_unit_fallbacks, 4 sha256_device_units, 5 lzma2_run_units, 6 lzma2_run_fallbacks
+// swc_stat counters (api.cpp), named as swc_stat's keys
+enum Stat { kStatLaunches, kStatUnits, kStatXzCacheHits, kStatDeflateUnitFallbacks, kStatSha256DeviceUnits, kStatLzma2RunUnits,
+            kStatLzma2RunFallbacks, kStatCount };
+void stat_add(Stat which, long long v);
 
 }  // namespace swc
 #endif
