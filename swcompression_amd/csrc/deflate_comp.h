@@ -1,8 +1,8 @@
 // deflate_comp.h -- Deflate COMPRESSION, one buffer per WAVEFRONT (the second piece of the encode side).
 //
 // Replaces Deflate.compress(data:) (reference Sources/Deflate/Deflate+Compress.swift:22-213): ONE block for the whole buffer --
-// static Huffman (RFC 1951 3.2.6) over a greedy LZ77 parse (minimum match 3, maximum 258, distances up to 32,768, the last
-// two bytes always literals, :146-213), or a stored block when that is not larger and the buffer fits its 16-bit length
+// static Huffman (RFC 1951 3.2.6) over a greedy LZ77 parse (minimum match 3, maximum 258, distances up to 32,768; no match
+// STARTS in the last two bytes, :155, but one may end on the last byte, :185, :146-213), or a stored block when that is not larger and the buffer fits its 16-bit length
 // (:30-45, with the reference's own size formula :48-83 applied to THIS parse).
 //
 // The reference finds matches through an exact dictionary of the most recent position of every three-byte group it has looked

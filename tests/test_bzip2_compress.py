@@ -60,13 +60,24 @@ def check_stream(x, z, level=1):
     assert z[:4] == b"BZh" + bytes([0x30 + level])
     raw = level * 80000
     blocks = [x[i:i + raw] for i in range(0, len(x), raw)]
-    # the first block starts behind the header, its stored CRC is that of its raw bytes; the trailer carries the combination
-    total = 0
+    # the first block starts behind the header, the others at any bit: the stored CRC of EVERY block is that of its raw bytes (the
+    # 48-bit magic is looked for at every bit offset); the trailer carries the combination
+    total, crcs = 0, []
     for b in blocks:
         c = O.bzip2crc32(b)
+        crcs.append(c)
         total = (((total << 1) | (total >> 31)) & 0xFFFFFFFF) ^ c
     if blocks:
         assert bits_at(z, 32, 48) == BLOCK_MAGIC and bits_at(z, 80, 32) == O.bzip2crc32(blocks[0])
+    bits = bin(int.from_bytes(b"\x01" + z, "big"))[3:]
+    magic, stored, at = "{:048b}".format(BLOCK_MAGIC), [], 0
+    while True:
+        at = bits.find(magic, at)
+        if at < 0:
+            break
+        stored.append(int(bits[at + 48:at + 80], 2))
+        at += 80
+    assert stored == crcs, "the stored CRCs of the blocks are not those of the raw blocks"
     # the end-of-stream marker and the combined CRC are the last 80 bits before the padding (at most 7 bits)
     found = False
     for pad in range(8):

@@ -1,0 +1,252 @@
+"""The four encoders on inputs BUILT against their parse (tests/_compress_cases.py), CPU tier: csrc/lz4_comp.h, csrc/deflate_comp.h
+(static and dynamic) and csrc/bzip2_comp.h on the host emulation, in the three lane orders.
+
+Every case: status and out_len; the output decodes to the input under the oracle's restatement of the reference decoder, which
+must consume all of it, and under zlib / liblz4 / libbz2; the case's expectation holds on the LISTING of the output (what the parse
+found: limits met exactly, end rules, emitter steps, header runs, table counts); the bytes do not depend on the lane order nor on
+where the buffers lie.  The listers are pinned against third-party encoders first.  A stand-alone program runs the LZ4 and Deflate
+cases under the address and undefined-behaviour sanitizers in allocations of exactly the contract's sizes."""
+import bz2
+import functools
+import struct
+import subprocess
+import zlib
+
+import pytest
+
+import _compress_cases as K
+import _deflate_build as DB
+import _emu as E
+import _emu_dynamic as D
+import _oracle as O
+from swcompression_amd import corpus
+from test_deflate_compress_dynamic import check_dynamic_header
+from test_lz4_compress import _liblz4_decode
+
+ORDERS = [0, 1, 2]
+DYNAMIC_CASES = K.DEFLATE + K.DYNAMIC
+
+
+# --------------------------------------------------------------------------------------------------------------- running a codec
+def _lz4(cases, **kw):
+    return E.lz4_compress([c.data for c in cases], [c.prefix for c in cases], **kw)
+
+
+def _static(cases, **kw):
+    return E.deflate_compress([c.data for c in cases], **kw)
+
+
+def _dynamic(cases, **kw):
+    return D.deflate_compress_dynamic([c.data for c in cases], **kw)
+
+
+CODECS = {"lz4": (K.LZ4, _lz4), "static": (K.DEFLATE, _static), "dynamic": (DYNAMIC_CASES, _dynamic)}
+
+
+@functools.lru_cache(maxsize=None)
+def results(codec, order=0):
+    """[(status, bytes, in_consumed, out_len)] of all cases of the codec in that lane order, computed once."""
+    cases, fn = CODECS[codec]
+    E.set_order(order)
+    try:
+        return fn(cases)
+    finally:
+        E.set_order(0)
+
+
+@functools.lru_cache(maxsize=None)
+def bzip2_results(order=0):
+    E.set_order(order)
+    try:
+        return [E.bzip2_compress(c.data, c.prefix) for c in K.BZIP2]           # (`prefix` of a bzip2 case: its level)
+    finally:
+        E.set_order(0)
+
+
+# ------------------------------------------------------------------------------------------------------------ the listers, pinned
+def test_deflate_lister_expands_zlib_streams():
+    """zlib at levels 0 / 1 / 9, Z_FIXED and the default strategy: stored, static and dynamic blocks, several per stream."""
+    kinds = set()
+    for x in (b"", b"a", corpus.p_text(70000, 1), corpus.p_mix(30000, 2), corpus.p_rand(3000, 3), bytes(5000), b"abc" * 3000):
+        for level in (0, 1, 9):
+            for strategy in (zlib.Z_FIXED, zlib.Z_DEFAULT_STRATEGY):
+                c = zlib.compressobj(level, zlib.DEFLATED, -15, 8, strategy)
+                z = c.compress(x) + c.flush()
+                blocks = K.deflate_tokens(z)
+                kinds |= set(b["btype"] for b in blocks)
+                assert (blocks[-1]["bits"][1] + 7) // 8 == len(z)
+                plain = bytearray()
+                for b in blocks:
+                    DB.expand(DB.normalise(b["tokens"]), plain)
+                assert bytes(plain) == x == K.deflate_expand(blocks), (len(x), level, strategy)
+    assert kinds == {0, 1, 2}
+
+
+def test_lz4_lister_expands_liblz4_and_oracle_blocks():
+    O.lib.refcpu_set_max_output(1 << 22)
+    try:
+        for x in (b"a", b"x" * 13, corpus.p_text(70001, 4), corpus.p_mix(30000, 5), corpus.p_rand(3000, 6), bytes(70000), b"abcd" * 5000):
+            for z in (corpus.lz4_block(x), O.lz4_compress_block(x)[1]):
+                seqs = K.lz4_sequences(z, strict=True)
+                assert K.lz4_expand(seqs) == x
+                assert sum(len(s[0]) + s[2] for s in seqs) == len(x)
+        pre, x = corpus.p_text(70000, 7), corpus.p_text(70000, 7)[100:30000]
+        seqs = K.lz4_sequences(O.lz4_compress_block(x, pre[-65536:])[1], strict=True)
+        assert K.lz4_expand(seqs, pre[-65536:]) == x
+    finally:
+        O.lib.refcpu_set_max_output(1 << 30)
+
+
+def test_bzip2_lister_on_libbz2_streams():
+    """bz2.compress: the symbol count the lister finds fits the selectors (a selector per 50 symbols), the stored CRCs are those of
+    the raw blocks (libbz2 cuts at level x 100,000 - 19 bytes of RLE1 output: one block here), the combined CRC follows."""
+    for x in (b"a", b"banana", corpus.p_text(60000, 8), corpus.p_mix(50000, 9), corpus.p_rand(20000, 10), bytes(90000), b"ab" * 30000):
+        for level in (1, 9):
+            z = bz2.compress(x, level)
+            lv, blocks, combined, used = K.bzip2_blocks(z)
+            assert lv == level and used == len(z) and len(blocks) == 1
+            b = blocks[0]
+            assert b["n_sel"] == -(-b["n_sym"] // 50), (b["n_sel"], b["n_sym"])
+            assert b["crc"] == K.bz_crc(x) == combined == O.bzip2crc32(x)
+            assert b["n_tables"] == K.bz_tables_for(b["n_sym"])
+
+
+# ------------------------------------------------------------------------------------------------------------------ the encoders
+@pytest.mark.parametrize("order", ORDERS)
+def test_lz4_cases(order):
+    O.lib.refcpu_set_max_output(1 << 22)
+    try:
+        for c, (st, z, cons, n), ref in zip(K.LZ4, results("lz4", order), results("lz4", 0)):
+            assert (st, n, cons) == (0, len(z), len(c.prefix) + len(c.data)), c.name
+            assert z == ref[1], "%s: the block depends on the order of the lanes" % c.name
+            if order == 0:
+                assert O.lz4_block(z, c.prefix[-65536:] or None)[:2] == (0, c.data), c.name
+                assert _liblz4_decode(z, len(c.data), c.prefix[-65536:]) == c.data, c.name
+                c.expect(K.lz4_sequences(z, strict=True))
+    finally:
+        O.lib.refcpu_set_max_output(1 << 30)
+
+
+def _check_deflate(c, z, kind):
+    assert zlib.decompress(z, -15) == c.data, c.name
+    assert O.deflate(z) == (0, c.data, len(z)), c.name
+    blocks = K.deflate_tokens(z)
+    assert (blocks[-1]["bits"][1] + 7) // 8 == len(z), c.name
+    if blocks[0]["btype"] == 2:
+        ll, dd = check_dynamic_header(z)
+        assert (ll, dd) == (blocks[0]["ll"], blocks[0]["dd"]), c.name
+    c.expect(blocks, kind)
+    return blocks
+
+
+@pytest.mark.parametrize("order", ORDERS)
+@pytest.mark.parametrize("kind", ["static", "dynamic"])
+def test_deflate_cases(kind, order):
+    cases = CODECS[kind][0]
+    for c, (st, z, cons, n), ref in zip(cases, results(kind, order), results(kind, 0)):
+        assert (st, n, cons) == (0, len(z), len(c.data)), c.name
+        assert z == ref[1], "%s: the stream depends on the order of the lanes" % c.name
+        if order == 0:
+            _check_deflate(c, z, kind)
+
+
+def test_dynamic_is_the_static_parse_and_deep_codes_are_deep():
+    """Both paths list the same tokens where both write a Huffman block; the precondition of the deep-code cases -- an unlimited
+    Huffman code over the lit/len counts of the parse is deeper than 15 -- holds, so the length limit is what their blocks show."""
+    st = dict(zip((c.name for c in K.DEFLATE), results("static")))
+    for c, r in zip(DYNAMIC_CASES, results("dynamic")):
+        a = K.deflate_tokens(r[1])
+        if c.name in st:
+            b = K.deflate_tokens(st[c.name][1])
+            assert len(r[1]) <= len(st[c.name][1]), c.name
+            if a[0]["btype"] and b[0]["btype"]:
+                assert a[0]["tokens"] == b[0]["tokens"], c.name
+        if c.family == "deep":
+            static_listing = K.deflate_tokens(E.deflate_compress([c.data])[0][1])
+            assert static_listing[0]["tokens"] == a[0]["tokens"]
+            ll, dd = K.litlen_counts(static_listing)
+            assert K.huffman_depth(ll) > 15, (c.name, K.huffman_depth(ll))
+    assert set(K.deflate_tokens(r[1])[0]["btype"] for r in results("dynamic")) == {0, 1, 2}
+
+
+@pytest.mark.parametrize("order", ORDERS)
+def test_bzip2_cases(order):
+    for c, (st, z), ref in zip(K.BZIP2, bzip2_results(order), bzip2_results(0)):
+        assert st == 0, c.name
+        assert z == ref[1], "%s: the stream depends on the order of the lanes" % c.name
+        if order == 0:
+            assert bz2.decompress(z) == c.data, c.name
+            assert O.bzip2(z) == (0, c.data, len(z)), c.name
+            listing = K.bzip2_blocks(z)
+            assert listing[3] == len(z), c.name
+            c.expect(listing)
+
+
+@pytest.mark.parametrize("kind", ["lz4", "static", "dynamic"])
+def test_placement_does_not_change_the_bytes(kind):
+    """Inputs one byte past a 16-byte boundary, outputs four (Deflate: `out` is 4-byte aligned by contract) or five (LZ4) past one,
+    in the guarded buffers of _emu.run_batch."""
+    cases, fn = CODECS[kind]
+    for c, r, ref in zip(cases, fn(cases, in_misalign=1, misalign=5 if kind == "lz4" else 4), results(kind)):
+        assert r == ref, c.name
+
+
+# --------------------------------------------------------------------------------------------------------------------- capacity
+def capacity_jobs(kind):
+    """[(case, out_cap, expected status, size)]: the capacity cases with out_cap = size and below it."""
+    cases = CODECS[kind][0]
+    sizes = dict(zip((c.name for c in cases), (r[3] for r in results(kind))))
+    jobs = []
+    for name in (K.LZ4_CAPACITY if kind == "lz4" else K.DEFLATE_CAPACITY):
+        size = sizes[name]
+        for d in (K.LZ4_CAPS if kind == "lz4" else K.DEFLATE_CAPS):
+            cap = 0 if d is None else 1 if d == "one" else size + d
+            assert 0 <= cap <= size
+            jobs.append((K.by_name(cases, name), cap, 0 if cap == size else 901, size))
+    return jobs
+
+
+@pytest.mark.parametrize("kind", ["lz4", "static", "dynamic"])
+def test_capacity(kind):
+    """Status 0 only where the stream fits; otherwise SWC_E_CAPACITY with the size needed, and nothing beyond out_cap (the guard
+    bytes of _emu.run_batch).  What was written within out_cap is the stream's beginning (the dynamic path writes nothing)."""
+    jobs = capacity_jobs(kind)
+    full = dict(zip((c.name for c in CODECS[kind][0]), (r[1] for r in results(kind))))
+    res = CODECS[kind][1]([j[0] for j in jobs], caps=[j[1] for j in jobs])
+    for (c, cap, status, size), (st, z, cons, n) in zip(jobs, res):
+        assert (st, n) == (status, size), (c.name, cap, st, n)
+        if status == 0 or kind != "dynamic":
+            assert z == full[c.name][:cap], (c.name, cap)
+
+
+# -------------------------------------------------------------------------------------------------------------- sanitizer program
+def case_file():
+    """u32 count; per job: u32 codec (0 LZ4, 1 static, 2 dynamic), u32 prefix length, u32 length of prefix + input, the bytes, u32
+    out_cap, i32 status, u32 out_len, u32 count + the bytes expected in [out, out + min(out_len, out_cap)) (count 0xFFFFFFFF: not
+    compared -- the dynamic path below its capacity)."""
+    out, count = bytearray(), 0
+    for code, kind in enumerate(("lz4", "static", "dynamic")):
+        cases = CODECS[kind][0]
+        jobs = [(c, None, r[0], r[3], r[1]) for c, r in zip(cases, results(kind))]
+        full = dict(zip((c.name for c in cases), (r[1] for r in results(kind))))
+        jobs += [(c, cap, st, size, full[c.name][:cap] if st == 0 or kind != "dynamic" else None) for c, cap, st, size in capacity_jobs(kind)]
+        for c, cap, st, size, data in jobs:
+            src = (c.prefix if kind == "lz4" else b"") + c.data
+            cap = (len(c.data) + len(c.data) // 255 + 16 if kind == "lz4" else len(c.data) + len(c.data) // 8 + 32) if cap is None else cap
+            out += struct.pack("<III", code, len(c.prefix) if kind == "lz4" else 0, len(src)) + src
+            out += struct.pack("<IiI", cap, st, size)
+            out += struct.pack("<I", 0xFFFFFFFF) if data is None else struct.pack("<I", len(data)) + data
+            count += 1
+    return struct.pack("<I", count) + bytes(out)
+
+
+def test_built_cases_under_the_sanitizers(tmp_path):
+    """tests/host_emu/emu_compress_built.cpp as a program of its own with -fsanitize=address,undefined: the input in a heap
+    allocation of exactly prefix + in_len bytes, the output in exactly out_cap bytes, the three lane orders; status, out_len and
+    bytes as the Python tier got them."""
+    exe = str(tmp_path / "emu_compress_built")
+    E.compile_program(exe, "emu_compress_built.cpp", "EMU_COMPRESS_BUILT_MAIN")
+    path = tmp_path / "cases.bin"
+    path.write_bytes(case_file())
+    p = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0 and "0 mismatches" in p.stdout, (p.stdout[-2000:], p.stderr[-4000:])
