@@ -1,14 +1,21 @@
-"""ctypes binding of tests/host_emu/libswc_emu.so -- the device code compiled for the host: the one library of the CPU tier, its one
-build recipe and its one rule for rebuilding.  The _emu_*.py modules are layers over `lib`.  TEST INFRASTRUCTURE ONLY (see
-tests/host_emu/emu.cpp)."""
+"""ctypes binding of tests/host_emu/libswc_emu.so -- the device code compiled for the host: the one library of the CPU tier (every
+entry point is in it), its variants under a -DSWC_SYNC_* switch of csrc/inflate_sync.h (libswc_emu.<tag>.so: one line of VARIANTS
+each), the one build recipe, the one rule for rebuilding and the one way to run a stand-alone sanitizer program.  The _emu_*.py
+modules are layers over `lib`.  TEST INFRASTRUCTURE ONLY (see tests/host_emu/emu.cpp)."""
 import ctypes as C
 import os
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _DIR = os.path.join(_HERE, "host_emu")
-_LIB = os.path.join(_DIR, "libswc_emu.so")
 _CSRC = os.path.join(os.path.dirname(_HERE), "swcompression_amd", "csrc")
+
+# tag -> (defines, what emu_pairs_enabled() says, what emu_sync_follow() says); None: the sources as they ship
+VARIANTS = {None: ((), 1, 1),
+            "nopairs": (("-DSWC_SYNC_NO_PAIRS=1",), 0, 1),
+            "nofollow": (("-DSWC_SYNC_NO_FOLLOW=1",), 1, 0),
+            "follow_held": (("-DSWC_SYNC_FOLLOW_HELD=1",), 1, 2)}
 
 
 class Job(C.Structure):
@@ -22,34 +29,84 @@ def _compile(out, src, opt, how):
                    ["-Wno-unknown-pragmas", "-pthread", "-o", out, os.path.join(_DIR, src)], check=True)
 
 
-def compile_lib(out, opt=("-O2", "-g")):
+def compile_lib(out, opt=("-O2", "-g"), defines=()):
     """The one recipe of the emulation library (emu.cpp includes the other sources); the ASAN tests pass their own optimisation and
     sanitizer flags."""
-    _compile(out, "emu.cpp", opt, ("-fPIC", "-shared"))
+    _compile(out, "emu.cpp", opt, ("-fPIC", "-shared") + tuple(defines))
 
 
-def compile_program(out, src, define, opt=("-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")):
+SANITIZED = ("-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
+
+
+def compile_program(out, src, define, opt=SANITIZED):
     """A source of host_emu that has a main of its own behind -D`define`, as a stand-alone program: by default with the address and
     undefined-behaviour sanitizers.  Run as a program, never loaded into python."""
     _compile(out, src, opt, ("-D" + define,))
 
 
-def build(force=False):
-    """Rebuilds the library when any source of host_emu or any header of csrc is newer than it."""
-    srcs = [os.path.join(_DIR, f) for f in os.listdir(_DIR) if f.endswith((".cpp", ".h"))]
-    srcs += [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
-    if not force and os.path.exists(_LIB) and all(os.path.getmtime(_LIB) >= os.path.getmtime(s) for s in srcs):
-        return
-    compile_lib(_LIB)
+def run_program(tmp_path, src, define, case_bytes, opt=SANITIZED, timeout=600):
+    """compile_program, then the program once on a file of `case_bytes`: asserts that it ends with status 0, returns what it printed."""
+    exe, cases = str(tmp_path / src[:-4]), str(tmp_path / "cases.bin")
+    compile_program(exe, src, define, opt)
+    with open(cases, "wb") as f:
+        f.write(case_bytes)
+    p = subprocess.run([exe, cases], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, errors="replace", timeout=timeout,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert p.returncode == 0, p.stdout[-4000:]
+    return p.stdout
 
 
-build()
-lib = C.CDLL(_LIB)
+def _path(tag):
+    return os.path.join(_DIR, "libswc_emu.so" if tag is None else "libswc_emu.%s.so" % tag)
+
+
+_newest = None   # the newest source's time: scanned once per process
+
+
+def _stale(path):
+    """The one rule: a library is rebuilt when any source of host_emu or any header of csrc is newer than it."""
+    global _newest
+    if _newest is None:
+        srcs = [os.path.join(_DIR, f) for f in os.listdir(_DIR) if f.endswith((".cpp", ".h"))]
+        srcs += [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
+        _newest = max(os.path.getmtime(s) for s in srcs)
+    return not os.path.exists(path) or os.path.getmtime(path) < _newest
+
+
+def _build_one(tag):
+    tmp = "%s.%d.tmp" % (_path(tag), os.getpid())
+    compile_lib(tmp, defines=VARIANTS[tag][0])
+    os.replace(tmp, _path(tag))   # (a process that has the old file loaded keeps it)
+
+
+def build(force=False, tags=tuple(VARIANTS)):
+    """Builds, in parallel, those of `tags` that are stale -- with `force`, all of them."""
+    todo = [t for t in tags if force or _stale(_path(t))]
+    with ThreadPoolExecutor(max(len(todo), 1)) as ex:
+        list(ex.map(_build_one, todo))
+
+
+_loaded = {}
+
+
+def load(tag=None):
+    """The library of a tag of VARIANTS, built if stale and held to what it says of itself."""
+    if tag not in _loaded:
+        build(tags=(tag,))
+        so = C.CDLL(_path(tag))
+        says = (so.emu_pairs_enabled(), so.emu_sync_follow())
+        assert says == VARIANTS[tag][1:], "%s says pairs %d, follow %d of itself" % ((_path(tag),) + says)
+        _loaded[tag] = so
+    return _loaded[tag]
+
+
+lib = load()
 
 
 def set_order(order):
-    """Thread order of the emulated SIMT regions (csrc/simt.h): 0 forward, 1 reverse, 2 shuffled."""
-    lib.emu_set_order(C.c_int(order))
+    """Thread order of the emulated SIMT regions (csrc/simt.h) in every library loaded so far: 0 forward, 1 reverse, 2 shuffled."""
+    for so in _loaded.values():
+        so.emu_set_order(C.c_int(order))
 
 
 class Guarded:

@@ -1,42 +1,17 @@
-"""A Deflate launch with linked units (csrc/inflate_sync.h, deflate_place.h, deflate_chain.h, lz_copy.h) on the host emulation: the
-binding of tests/host_emu/emu_deflate_linked.cpp, a library of its own built with _emu's recipe.  TEST INFRASTRUCTURE ONLY."""
+"""A Deflate launch with linked units (csrc/inflate_sync.h, deflate_place.h, deflate_chain.h, lz_copy.h) on the host emulation: a
+thin layer over _emu (tests/host_emu/emu_deflate_linked.cpp).  TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
-import os
 import struct
 
 import _emu
 from _emu import Job
 
-_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_emu")
-_LIB = os.path.join(_DIR, "libswc_emu_deflate_linked.so")
-_CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "swcompression_amd", "csrc")
+lib = _emu.lib
+set_order = _emu.set_order
 
 GUARD = 16
 JOINED, OPEN, LINKED = 1, 2, 4
 RESOLVER, COPIER, BODY_ALONE = 0, 1, 2   # the arrangements of phase 2 (emu_deflate_linked.cpp)
-
-
-def build():
-    srcs = [os.path.join(_DIR, f) for f in os.listdir(_DIR) if f.endswith((".cpp", ".h"))]
-    srcs += [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
-    if os.path.exists(_LIB) and all(os.path.getmtime(_LIB) >= os.path.getmtime(s) for s in srcs):
-        return
-    tmp = "%s.%d.tmp" % (_LIB, os.getpid())
-    _emu._compile(tmp, "emu_deflate_linked.cpp", ("-O2", "-g"), ("-fPIC", "-shared"))
-    os.replace(tmp, _LIB)
-
-
-build()
-lib = C.CDLL(_LIB)
-
-
-def set_order(order):
-    lib.emu_set_order(C.c_int(order))
-
-
-def compile_program(out):
-    """The stand-alone program of emu_deflate_linked.cpp (its own main), with the address and undefined-behaviour sanitizers."""
-    _emu.compile_program(out, "emu_deflate_linked.cpp", "EMU_DEFLATE_LINKED_MAIN")
 
 
 def run_units(units, misalign=0, arrangement=COPIER, team=0, reversed_=False, crc=False):
@@ -84,8 +59,8 @@ def run_units(units, misalign=0, arrangement=COPIER, team=0, reversed_=False, cr
     return res
 
 
-def write_cases(path, cases):
-    """The file the stand-alone program reads.  cases: list of (units, expected) with expected per job (status, out_len, in_consumed,
+def case_file(cases):
+    """The bytes of the file the stand-alone program reads.  cases: list of (units, expected) with expected per job (status, out_len, in_consumed,
     aux, bytes) as _deflate_linked_cases.expect gives it."""
     out = bytearray(struct.pack("<I", len(cases)))
     for units, exp in cases:
@@ -95,5 +70,4 @@ def write_cases(path, cases):
             data = data if pin == 2 else b""
             out += struct.pack("<iI", u["aux"], len(u["data"])) + bytes(u["data"])
             out += struct.pack("<IiIIiII", u["cap"], st, pin, n if pin else 0, aux, cons if pin else 0, len(data)) + data
-    with open(path, "wb") as f:
-        f.write(out)
+    return bytes(out)

@@ -13,11 +13,6 @@ GUARD = 16
 JOINED, OPEN = 1, 2
 
 
-def compile_program(out):
-    """The stand-alone program of emu_deflate_units.cpp (its own main), with the address and undefined-behaviour sanitizers."""
-    _emu.compile_program(out, "emu_deflate_units.cpp", "EMU_DEFLATE_UNITS_MAIN")
-
-
 def place(sizes, caps, aux, base=0x10000, reversed_=False):
     """The placing scan alone: jobs with out_len = sizes[i], out_cap = caps[i], aux[i]; every job that is not joined gets
     out = base + 2^32 * i.  Returns per job (out, status, out_len); status 902 where the scan wrote none."""
@@ -74,8 +69,8 @@ def run_units(units, misalign=0, copier=1, team=0, reversed_=False, head_gap=Non
     return res
 
 
-def write_cases(path, cases):
-    """The file the stand-alone program reads.  cases: list of (units, expected) with expected per job (status, out_len, in_consumed,
+def case_file(cases):
+    """The bytes of the file the stand-alone program reads.  cases: list of (units, expected) with expected per job (status, out_len, in_consumed,
     aux, bytes) as _deflate_units_cases.expect gives it: out_len None = a failed unit, of which only status and aux are compared."""
     out = bytearray(struct.pack("<I", len(cases)))
     for units, exp in cases:
@@ -85,5 +80,4 @@ def write_cases(path, cases):
             data = data if pinned else b""
             out += struct.pack("<iI", u["aux"], len(u["data"])) + bytes(u["data"])
             out += struct.pack("<IiIIiII", u["cap"], st, 1 if pinned else 0, n if pinned else 0, aux, cons if pinned else 0, len(data)) + data
-    with open(path, "wb") as f:
-        f.write(out)
+    return bytes(out)

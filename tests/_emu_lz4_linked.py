@@ -12,11 +12,6 @@ set_order = _emu.set_order
 GUARD = 16
 
 
-def compile_program(out):
-    """The stand-alone program of emu_lz4_linked.cpp (its own main), with the address and undefined-behaviour sanitizers."""
-    _emu.compile_program(out, "emu_lz4_linked.cpp", "EMU_LZ4_LINKED_MAIN")
-
-
 def run_chains(chains, misalign=0, copier=1):
     """Chains (tests/_lz4_linked_cases.py) as ONE job list through one emulated launch -- copier: 1 = of kCopierMin jobs and more (one
     record-mode parse, the chain copier over all jobs), 0 = a smaller one (the four-kernel split).  Every chain has a buffer of its
@@ -79,8 +74,8 @@ def jobs_taken(reset=True):
     return st[5]
 
 
-def write_cases(path, cases, expected):
-    """The file the stand-alone program reads: `cases` with what the oracle says (expected(case) -> per job (status, bytes, out_len))."""
+def case_file(cases, expected):
+    """The bytes of the file the stand-alone program reads: `cases` with what the oracle says (expected(case) -> per job (status, bytes, out_len))."""
     out = bytearray(struct.pack("<I", len(cases)))
     for ch in cases:
         exp = expected(ch)
@@ -90,5 +85,4 @@ def write_cases(path, cases, expected):
             out += struct.pack("<iI", j["aux"], len(j["data"])) + j["data"] + struct.pack("<IiI", j["cap"], st, n)
         want = b"".join(e[1] for e in exp)
         out += struct.pack("<I", len(want)) + want
-    with open(path, "wb") as f:
-        f.write(out)
+    return bytes(out)

@@ -15,12 +15,6 @@ RECIPE_DICT_BYTE = 8   # 64 KiB: what recipe() hands to liblzma
 SHAPES = [(0, 4, 4), (3, 0, 2), (1, 3, 4), (4, 0, 0)]
 
 
-def compile_program(out):
-    """The stand-alone program of emu_lzma2_runs.cpp (its own main), with the address and undefined-behaviour sanitizers."""
-    # (unoptimised: the program holds the whole emulation library, and its two cases take no time to run)
-    _emu.compile_program(out, "emu_lzma2_runs.cpp", "EMU_LZMA2_RUNS_MAIN", opt=("-O0", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
-
-
 def recipe(parts, shape=(3, 0, 2)):
     """One LZMA2 stream (chunks only, no dictionary-size byte) of independently compressed parts: liblzma's raw LZMA2 of every part
     without its end marker, one end marker behind the last.  Every part opens with a chunk that resets dictionary, state and
@@ -136,13 +130,12 @@ def accept(refs, res):
     return b"".join(r[1] for r in res), refs[-1][0] + res[-1][2]
 
 
-def write_cases(path, cases):
-    """The file the stand-alone program reads.  cases: list of (chunks, refs, consumed, plain), refs as accept() takes them."""
+def case_file(cases):
+    """The bytes of the file the stand-alone program reads.  cases: list of (chunks, refs, consumed, plain), refs as accept() takes them."""
     out = bytearray(struct.pack("<I", len(cases)))
     for chunks, refs, consumed, plain in cases:
         out += struct.pack("<I", len(chunks)) + bytes(chunks) + struct.pack("<I", len(refs))
         for off, comp, uncomp, aux in refs:
             out += struct.pack("<IIII", off, comp, uncomp, aux)
         out += struct.pack("<II", consumed, len(plain)) + bytes(plain)
-    with open(path, "wb") as f:
-        f.write(out)
+    return bytes(out)

@@ -1,35 +1,14 @@
-"""SHA-256 by one lane per job (csrc/sha256_lane.h, the body of csrc/job_kernels.h) on the host emulation: the binding of
-tests/host_emu/emu_sha256.cpp, a library of its own built with _emu's recipe.  TEST INFRASTRUCTURE ONLY."""
+"""SHA-256 by one lane per job (csrc/sha256_lane.h, the body of csrc/job_kernels.h) on the host emulation: a thin layer over
+_emu (tests/host_emu/emu_sha256.cpp).  TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
-import os
 
 import _emu
 from _emu import Job
 from _sha256_cases import LENGTHS, message, mix  # noqa: F401
 
-_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_emu")
-_LIB = os.path.join(_DIR, "libswc_emu_sha256.so")
-_CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "swcompression_amd", "csrc")
-
-def build():
-    srcs = [os.path.join(_DIR, f) for f in os.listdir(_DIR) if f.endswith((".cpp", ".h"))]
-    srcs += [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
-    if os.path.exists(_LIB) and all(os.path.getmtime(_LIB) >= os.path.getmtime(s) for s in srcs):
-        return
-    tmp = "%s.%d.tmp" % (_LIB, os.getpid())
-    _emu._compile(tmp, "emu_sha256.cpp", ("-O2", "-g"), ("-fPIC", "-shared"))
-    os.replace(tmp, _LIB)
-
-
-build()
-lib = C.CDLL(_LIB)
+lib = _emu.lib
 lib.emu_sha256_jobs.argtypes = [C.POINTER(Job), C.c_size_t, C.c_void_p]
 lib.emu_sha256_jobs.restype = None
-
-
-def compile_program(out):
-    """The stand-alone program of emu_sha256.cpp (its own main), with the address and undefined-behaviour sanitizers."""
-    _emu.compile_program(out, "emu_sha256.cpp", "EMU_SHA256_MAIN")
 
 
 def run(jobs, residue=0, digest_residue=1):

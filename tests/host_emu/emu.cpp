@@ -5,8 +5,9 @@
 // linked into libswc_hip.so.  A driver that emulates a launch calls the kernel bodies of csrc/job_kernels.h -- what the __global__
 // functions call -- in the order the launcher issues the kernels; the other entry points test one header function alone.  This
 // file is the whole library: the drivers that have a source of their own (emu_bgzf.cpp, emu_crc_tail.cpp, emu_lz4_linked.cpp --
-// every LZ4 decode launch --, emu_deflate_units.cpp -- every Deflate decode launch) are included at its end, so that one compile
-// shares the template instantiations.
+// every LZ4 decode launch --, emu_deflate_units.cpp -- every Deflate decode launch --, emu_deflate_linked.cpp, emu_sha256.cpp and
+// the probes of emu_deflate_phase1.cpp) are included at its end, so that one compile shares the template instantiations.  A
+// differential variant is this file under one more -D (tests/_emu.py: VARIANTS).
 #include <algorithm>
 #include <memory>
 #include "emu_util.h"
@@ -364,8 +365,11 @@ extern "C" int emu_bzip2_compress(const uint8_t* data, size_t len, int level, ui
     return st;
 }
 
-// ---- the drivers that have a source of their own (two of them double as stand-alone sanitizer programs) ----------------------
+// ---- the drivers that have a source of their own (four of them double as stand-alone sanitizer programs) ---------------------
 #include "emu_bgzf.cpp"
 #include "emu_crc_tail.cpp"
 #include "emu_lz4_linked.cpp"
 #include "emu_deflate_units.cpp"
+#include "emu_deflate_linked.cpp"
+#include "emu_sha256.cpp"
+#include "emu_deflate_phase1.cpp"

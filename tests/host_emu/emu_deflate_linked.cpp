@@ -1,8 +1,9 @@
 // emu_deflate_linked.cpp -- TEST INFRASTRUCTURE.  A Deflate launch with units that share history (SWC_DEFLATE_LINKED) compiled for the
 // HOST (g++ -DSWC_HOST_EMULATION): phase 1 -- one wave or the team --, the placing scan, and phase 2 as launch_inflate_phase2 issues
 // it: the copy kernel (or, below the wave copier's threshold, the resolver), each skipping the chains, then the chain kernel
-// (csrc/deflate_chain.h), with or without the CRC tail; the bodies of csrc/job_kernels.h called first-to-last or last-to-first.  A
-// library of its own (tests/_emu_deflate_linked.py); it takes phase 1 and the scan from emu_deflate_units.cpp.  Never shipped.
+// (csrc/deflate_chain.h), with or without the CRC tail; the bodies of csrc/job_kernels.h called first-to-last or last-to-first.  Part
+// of libswc_emu.so (emu.cpp includes it; tests/_emu_deflate_linked.py); it takes phase 1 and the scan from emu_deflate_units.cpp.
+// Never shipped.
 //
 // With -DEMU_DEFLATE_LINKED_MAIN the file is a stand-alone program (for -fsanitize=address,undefined): it reads runs and what is
 // expected of them from a file written by tests/test_deflate_linked_emulation.py and runs every case in the three lane orders, with

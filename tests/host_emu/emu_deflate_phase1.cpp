@@ -1,11 +1,11 @@
-// emu_deflate_pairs.cpp -- TEST INFRASTRUCTURE.  What tests/test_deflate_pairs_emulation.py needs beyond libswc_emu.so: the direct
-// tables sync_tables_from_lengths (csrc/inflate_sync.h) builds from a set of code lengths, read back, and phase 1 of one stream with
-// what it leaves in the workspace (stream header, record list, literal stream).  A library of its own (this file includes emu.cpp,
-// so every driver of the emulation is in it as well), built twice by tests/_emu_deflate_pairs.py: as the sources are, and with
-// -DSWC_SYNC_NO_PAIRS=1 -- the entry format without pairs.  Never shipped.
-#include "emu.cpp"
+// emu_deflate_phase1.cpp -- TEST INFRASTRUCTURE.  The probes of Deflate phase 1 (tests/_emu_deflate_phase1.py): which of the
+// -DSWC_SYNC_* switches of csrc/inflate_sync.h the library was built under, the direct tables sync_tables_from_lengths builds from
+// a set of code lengths, read back, and phase 1 of one stream with what it leaves in the workspace (stream header, record list,
+// literal stream).  Part of libswc_emu.so and of each of its variants (emu.cpp includes it).  Never shipped.
+#include "emu_deflate_units.cpp"
 
 extern "C" int emu_pairs_enabled() { return SWC_SYNC_NO_PAIRS ? 0 : 1; }
+extern "C" int emu_sync_follow() { return SWC_SYNC_FOLLOW; }
 extern "C" int emu_pairs_lit_bits() { return swc::inflate::kSyncLitBits; }
 
 // lens[0 .. literals + distances): the code lengths of a block.  lut_out: the (1 << kSyncLitBits) + 256 direct entries.  Returns

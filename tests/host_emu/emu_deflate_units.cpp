@@ -6,6 +6,8 @@
 // expected of them from a file written by tests/test_deflate_units_emulation.py, runs every case at the sixteen alignments of its
 // buffers, in the three lane orders, with both copiers, both copy orders, the team instantiation of phase 1 and the CRC form of the
 // copy, and compares; the placing scan runs on the size lists of the same test as well.
+#ifndef EMU_DEFLATE_UNITS_CPP   // (not #pragma once: this is also the main file of its own program)
+#define EMU_DEFLATE_UNITS_CPP
 #include "emu_util.h"
 #include "../../swcompression_amd/csrc/deflate_place.h"
 
@@ -189,3 +191,4 @@ int main(int argc, char** argv) {
     return bad ? 1 : 0;
 }
 #endif
+#endif   // EMU_DEFLATE_UNITS_CPP

@@ -1,6 +1,6 @@
 // emu_sha256.cpp -- TEST INFRASTRUCTURE.  A launch of swc_sha256_kernel (csrc/sha256_lane.h: one job per lane) compiled for the HOST
-// (g++ -DSWC_HOST_EMULATION): the body of csrc/job_kernels.h for every lane of every wave of the grid launch_sha256 issues.  A
-// library of its own (tests/_emu_sha256.py).  Never shipped.
+// (g++ -DSWC_HOST_EMULATION): the body of csrc/job_kernels.h for every lane of every wave of the grid launch_sha256 issues.  Part
+// of libswc_emu.so (emu.cpp includes it; tests/_emu_sha256.py).  Never shipped.
 //
 // With -DEMU_SHA256_MAIN the file is a stand-alone program (for -fsanitize=address,undefined): it reads lengths and the digests
 // expected of them from a file written by tests/test_sha256_emulation.py and hashes every message at the sixteen residues of its

@@ -1,6 +1,6 @@
-// emu_util.h -- TEST INFRASTRUCTURE.  What the sources of the host emulation share.  libswc_emu.so is ONE translation unit
-// (emu.cpp, which includes the other emu_*.cpp at its end); a stand-alone sanitizer program is one of those sources alone with its
-// -D..._MAIN.  Either way this header is read once per link, so the one emu_set_order is defined here.  Never shipped.
+// emu_util.h -- TEST INFRASTRUCTURE.  What the sources of the host emulation share.  libswc_emu.so, like each of its
+// variants, is ONE translation unit (emu.cpp, which includes the other emu_*.cpp at its end); a stand-alone sanitizer program is one
+// of those sources alone with its -D..._MAIN.  Either way this header is read once per link, so the one emu_set_order is defined here.  Never shipped.
 #pragma once
 #include <vector>
 #include <cstring>

@@ -9,7 +9,7 @@ import zlib
 import pytest
 
 import _deflate_follow_cases as FC
-import _emu_deflate_follow as F
+import _emu_deflate_phase1 as F
 import _oracle as O
 from swcompression_amd import corpus
 
@@ -85,7 +85,7 @@ def test_the_emulated_decoder_takes_the_follow_ups_of_the_model():
         if name.startswith("pending-literals"):
             continue                                    # (two blocks: the model covers the second)
         base = F.counted(F.single, c[1], _cap(c))[4]
-        for lib, model in ((F.follow, _STEPS[name]), (F.held, _STEPS_HELD[name])):
+        for lib, model in ((F.shipped, _STEPS[name]), (F.held, _STEPS_HELD[name])):
             assert base - F.counted(lib, c[1], _cap(c))[4] == sum(s[3] for s in model), name
 
 
@@ -93,14 +93,14 @@ def test_directed_streams_phase_1_is_the_one_with_one_code_per_step(order, team)
     for c in CASES:
         for aux in (0, 1 | 4):          # alone; SWC_DEFLATE_JOINED | SWC_DEFLATE_LINKED: distances may reach into a history
             want = F.phase1(F.single, c[1], _cap(c), aux, team)
-            assert F.phase1(F.follow, c[1], _cap(c), aux, team) == want, (c[0], aux)
+            assert F.phase1(F.shipped, c[1], _cap(c), aux, team) == want, (c[0], aux)
             assert F.phase1(F.held, c[1], _cap(c), aux, team) == want, (c[0], aux, "held window")
 
 
 def test_directed_streams_against_the_oracle(order, team):
     zs, caps = [c[1] for c in CASES], [_cap(c) for c in CASES]
     ref = F.inflate(F.single, zs, caps)
-    for lib in (F.follow, F.held):
+    for lib in (F.shipped, F.held):
         res = F.inflate(lib, zs, caps)
         for c, r, q in zip(CASES, res, ref):
             st, out, cons = EXPECTED[c[0]]
@@ -114,7 +114,7 @@ def test_capacity_inside_a_follow_up_run(team):
     c = next(c for c in CASES if c[0] == "group-nine")
     out = EXPECTED[c[0]][1]
     for cap in (len(out) - 1, len(out) - 4, 301, 302):
-        got = F.inflate(F.follow, [c[1]], [cap])
+        got = F.inflate(F.shipped, [c[1]], [cap])
         assert got == F.inflate(F.single, [c[1]], [cap]) and got[0][1] == out[:cap]
 
 
@@ -137,9 +137,9 @@ def test_members_of_64k_against_zlib(kind, order, team):
     assert zlib.decompress(z, -15) == plain
     want = F.phase1(F.single, z, len(plain), 0, team)
     assert want[:3] == (0, len(plain), len(z))
-    assert F.phase1(F.follow, z, len(plain), 0, team) == want
+    assert F.phase1(F.shipped, z, len(plain), 0, team) == want
     assert F.phase1(F.held, z, len(plain), 0, team) == want
-    assert F.inflate(F.follow, [z], [len(plain)]) == [(0, plain, len(z), len(plain))]
+    assert F.inflate(F.shipped, [z], [len(plain)]) == [(0, plain, len(z), len(plain))]
 
 
 def test_small_streams_phase_1(order, team):
@@ -147,5 +147,5 @@ def test_small_streams_phase_1(order, team):
         st, out, cons = O.deflate(z)
         assert st == 0
         want = F.phase1(F.single, z, len(out), 0, team)
-        assert F.phase1(F.follow, z, len(out), 0, team) == want and F.phase1(F.held, z, len(out), 0, team) == want, k
+        assert F.phase1(F.shipped, z, len(out), 0, team) == want and F.phase1(F.held, z, len(out), 0, team) == want, k
         assert want[:3] == (0, len(out), cons)

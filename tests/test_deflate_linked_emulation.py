@@ -3,14 +3,13 @@ reach it notes (csrc/inflate_sync.h, one wave and the team), the placing scan, a
 in the host emulation, under the three lane orders, in every arrangement of phase 2 and both orders of the bodies, against units
 built token by token, zlib's own sync-flushed output and the oracle (_deflate_linked_cases); the stand-alone program under ASan +
 UBSan on the same cases."""
-import os
-import subprocess
 import zlib
 
 import pytest
 
 import _deflate_linked_cases as L
 import _deflate_units_cases as K
+import _emu
 import _emu_deflate_linked as E
 
 ORDERS = [0, 1, 2]
@@ -226,8 +225,6 @@ def test_standalone_program_sanitized(tmp_path, expected, sync_flushed):
     """tests/host_emu/emu_deflate_linked.cpp as a program of its own under ASan + UBSan on the same cases: 3 lane orders x both forms of
     phase 1 x the three arrangements of phase 2 x both orders of the bodies x four alignments (the long cases: every combination once),
     in allocations of exactly the lines the contract names."""
-    exe = str(tmp_path / "emu_deflate_linked")
-    E.compile_program(exe)
     cases = [(RUNS[name], expected[name]) for name in RUNS]
     for run in L.residue_runs()[::3]:
         cases.append((run, L.expect(run)))
@@ -235,9 +232,5 @@ def test_standalone_program_sanitized(tmp_path, expected, sync_flushed):
     jobs = L.tiles_run()
     cases.append((jobs, [K.expect(dict(u, open_plain=None))[:5] for u in jobs[:60]] + L.expect(jobs[60:])))
     cases.append((sync_flushed[3], sync_flushed[4]))
-    path = str(tmp_path / "cases.bin")
-    E.write_cases(path, cases)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
-    p = subprocess.run([exe, path], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=env)
-    assert p.returncode == 0, p.stdout.decode(errors="replace")[-4000:]
-    assert b"%d cases, 0 mismatches" % len(cases) in p.stdout
+    out = _emu.run_program(tmp_path, "emu_deflate_linked.cpp", "EMU_DEFLATE_LINKED_MAIN", E.case_file(cases))
+    assert "%d cases, 0 mismatches" % len(cases) in out

@@ -8,7 +8,7 @@ import pytest
 
 import _deflate_build as B
 import _deflate_pairs_cases as PC
-import _emu_deflate_pairs as P
+import _emu_deflate_phase1 as P
 import _oracle as O
 
 LIT_BITS, DIST_BITS = P.LIT_BITS, P.DIST_BITS
@@ -113,7 +113,7 @@ def _check_tables(lit, dist, what):
     """Every direct entry of both builds against the scalar decode; returns the number of pair entries."""
     lcodes, dcodes = _by_prefix(lit), _by_prefix(dist)
     n_pairs = 0
-    for lib, pairs in ((P.pairs, True), (P.plain, False)):
+    for lib, pairs in ((P.shipped, True), (P.plain, False)):
         fast, ltab, dtab = P.tables(lib, lit, dist)
         assert fast, what   # (no set here is over-subscribed or deeper than the subtables hold)
         for idx in range(1 << DIST_BITS):
@@ -160,7 +160,7 @@ def test_directed_sets_hold_what_they_were_built_for():
     lc, dc = _by_prefix(lit), _by_prefix(dist)
     got = {_ref_lit(lc, dc, i, True)[0] for i in range(1 << LIT_BITS) if i & 1 == B._reverse(B._ref_codes(lit)[257][0], 1)}
     assert got == {"pair", "len"}                          # distance codes of up to 8 bits pair, the links behind 9 and 10 do not
-    _, ltab, _ = P.tables(P.pairs, lit, dist)
+    _, ltab, _ = P.tables(P.shipped, lit, dist)
     assert max((e & 31) - 2 for e in ltab if e >> 28 & 1 and e >> 30 & 1 == 0) <= LIT_BITS + 13
 
 
@@ -214,7 +214,7 @@ def test_the_case_streams_are_made_of_pairs():
 
 def test_directed_streams_against_the_oracle(order, team):
     caps = [cap if cap is not None else max(len(e[1]), 1) for (_, _, cap), e in zip(CASES, EXPECTED)]
-    res = P.inflate(P.pairs, [z for _, z, _ in CASES], caps)
+    res = P.inflate(P.shipped, [z for _, z, _ in CASES], caps)
     ref = P.inflate(P.plain, [z for _, z, _ in CASES], caps)
     for (name, _, cap), e, r, q in zip(CASES, EXPECTED, res, ref):
         st, out, cons, n = r
@@ -231,7 +231,7 @@ def test_directed_streams_phase_1_is_the_one_without_pairs(order, team):
     for name, z, cap in CASES:
         cap = cap if cap is not None else max(len(_BY_NAME[name][1]), 1)
         for aux in (0, 1 | 4):          # alone; SWC_DEFLATE_JOINED | SWC_DEFLATE_LINKED: distances may reach into a history
-            assert P.phase1(P.pairs, z, cap, aux, team) == P.phase1(P.plain, z, cap, aux, team), (name, aux)
+            assert P.phase1(P.shipped, z, cap, aux, team) == P.phase1(P.plain, z, cap, aux, team), (name, aux)
 
 
 def test_linked_unit_pair_reaches_into_its_history(team):
@@ -247,7 +247,7 @@ def test_linked_unit_pair_reaches_into_its_history(team):
             s.put(97)
         s.put(("sym", 258, 0) + B._DIST_SYM[distance], 98)
         s.eob()
-        got = P.phase1(P.pairs, s.data(), 64, 1 | 4, team)
+        got = P.phase1(P.shipped, s.data(), 64, 1 | 4, team)
         assert got == P.phase1(P.plain, s.data(), 64, 1 | 4, team)
         assert got[0] == 0 and got[1] == at + 5 and got[5] == distance - at, (at, distance, got[:7])
 
@@ -301,11 +301,11 @@ def test_zlib_streams_phase_1_and_output_equal_the_format_without_pairs(part):
         z = c.compress(text) + c.flush()
         P.set_order(k % 3)
         team = (k // 3) % 2
-        a, b = P.phase1(P.pairs, z, n, 0, team), P.phase1(P.plain, z, n, 0, team)
+        a, b = P.phase1(P.shipped, z, n, 0, team), P.phase1(P.plain, z, n, 0, team)
         assert a == b, "part %d stream %d: phase 1 differs" % (part, k)
         assert a[:3] == (0, n, len(z))
         if k % 10 == 0:
             P.set_team(team)
-            assert P.inflate(P.pairs, [z], [n]) == [(0, text, len(z), n)]
+            assert P.inflate(P.shipped, [z], [n]) == [(0, text, len(z), n)]
             P.set_team(0)
     P.set_order(0)

@@ -2,13 +2,12 @@
 copy at any byte address (csrc/lz_copy.h, lz_resolve.h) in the host emulation, under the three lane orders, against units built
 code by code (_deflate_units_cases) and the oracle; the stand-alone program under ASan + UBSan on the same cases."""
 import ctypes as C
-import os
-import subprocess
 import zlib
 
 import pytest
 
 import _deflate_units_cases as K
+import _emu
 import _emu_deflate_units as E
 
 ORDERS = [0, 1, 2]
@@ -173,8 +172,6 @@ def test_standalone_program_sanitized(tmp_path, expected):
     failed unit the status and aux), JOINED on job 0, residue pairs, the long run across tiles, and the place-scan lists (built into
     the program) -- 16 alignments x 3 lane orders x both copiers x both copy orders, the team instantiation of phase 1 and the CRC form of the copy, in
     allocations of exactly the lines the contract names."""
-    exe = str(tmp_path / "emu_deflate_units")
-    E.compile_program(exe)
     cases = [(RUNS[name], expected[name]) for name in RUNS]
     run = RUNS["stored-markers"]
     orphans = [dict(run[1]), dict(run[2])]
@@ -184,9 +181,5 @@ def test_standalone_program_sanitized(tmp_path, expected):
         cases.append((pair, [K.expect(u) for u in pair]))
     long_ = K.long_run()
     cases.append((long_, [K.expect(u) for u in long_]))
-    path = str(tmp_path / "cases.bin")
-    E.write_cases(path, cases)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
-    p = subprocess.run([exe, path], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=env)
-    assert p.returncode == 0, p.stdout.decode(errors="replace")[-4000:]
-    assert b"%d cases, 0 mismatches" % len(cases) in p.stdout
+    out = _emu.run_program(tmp_path, "emu_deflate_units.cpp", "EMU_DEFLATE_UNITS_MAIN", E.case_file(cases))
+    assert "%d cases, 0 mismatches" % len(cases) in out

@@ -1,11 +1,9 @@
 """CPU tier of the linked LZ4 blocks: the host build of the parse with history (csrc/lz4_wave.h), the copier with history
 (csrc/lz_copy.h) and the chain walk (csrc/lz4_chain.h) -- tests/host_emu/emu_lz4_linked.cpp -- against the oracle, block by block
 with the 64 KiB suffix rule: in three lane orders, with the head's output at every misalignment, guard bytes on both sides."""
-import os
-import subprocess
-
 import pytest
 
+import _emu
 import _emu_lz4_linked as E
 import _lz4_linked_cases as K
 import _oracle as O
@@ -141,15 +139,9 @@ def test_frames_whole():
 def test_stand_alone_program_with_sanitizers(tmp_path):
     """Cases 1-6 in a program of its own, built with the address and undefined-behaviour sanitizers: every chain in exactly the
     bytes the job contract names, at sixteen alignments, in three lane orders."""
-    exe = os.path.join(str(tmp_path), "emu_lz4_linked_main")
-    cases = os.path.join(str(tmp_path), "cases.bin")
-    E.compile_program(exe)
-
     def exp(ch):
         return [(st, out, 0 if n is None else n) for st, out, n in K.expected(ch)]
-    E.write_cases(cases, K.sanitizer_cases(), exp)
-    p = subprocess.run([exe, cases], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout + p.stderr
+    _emu.run_program(tmp_path, "emu_lz4_linked.cpp", "EMU_LZ4_LINKED_MAIN", E.case_file(K.sanitizer_cases(), exp))
 
 
 def test_index_blocks_flags():

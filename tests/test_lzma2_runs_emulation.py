@@ -3,10 +3,10 @@ the host emulation, both model layouts), swc_index_blocks kind 8, and the units 
 include/swc_hip.h -- against the oracle and the expectations of the stream builder (tests/_lzma_build.py)."""
 import functools
 import random
-import subprocess
 
 import pytest
 
+import _emu
 import _emu_lzma2_runs as R
 import _lzma_build as B
 import _oracle as O
@@ -292,10 +292,6 @@ def test_stand_alone_program_with_sanitizers(tmp_path):
     _, parts, z = recipe_cases()[1]
     cases = [(c.stream, units_of(c.stream, c.dict_byte), c.consumed, c.plain), (z, units_of(z, DB), len(z), b"".join(parts))]
     assert all(len(refs) >= 3 for _, refs, _, _ in cases)
-    path = str(tmp_path / "cases.bin")
-    exe = str(tmp_path / "emu_lzma2_runs")
-    R.write_cases(path, cases)
-    R.compile_program(exe)
-    p = subprocess.run([exe, path], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
-    assert p.returncode == 0, p.stdout.decode(errors="replace")
-    assert b"2 cases, 0 mismatches" in p.stdout
+    # (unoptimised: the program holds the whole emulation library, and its two cases take no time to run)
+    out = _emu.run_program(tmp_path, "emu_lzma2_runs.cpp", "EMU_LZMA2_RUNS_MAIN", R.case_file(cases), opt=("-O0",) + _emu.SANITIZED[1:])
+    assert "2 cases, 0 mismatches" in out

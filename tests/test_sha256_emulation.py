@@ -5,10 +5,10 @@ import hashlib
 import json
 import os
 import struct
-import subprocess
 
 import pytest
 
+import _emu
 import _emu_sha256 as E
 import _oracle as O
 
@@ -55,14 +55,6 @@ def test_launch_of_mixed_jobs(n):
 def test_standalone_program_sanitized(tmp_path):
     """tests/host_emu/emu_sha256.cpp as a program of its own under ASan + UBSan: every length at the 16 residues, the message the last
     bytes of its heap allocation, alone and as one lane of a launch of all lengths; a byte read behind a message is a heap overflow."""
-    exe = str(tmp_path / "emu_sha256")
-    E.compile_program(exe)
-    path = str(tmp_path / "cases.bin")
-    with open(path, "wb") as f:
-        f.write(struct.pack("<I", len(E.LENGTHS)))
-        for n in E.LENGTHS:
-            f.write(struct.pack("<I", n) + hashlib.sha256(E.message(n)).digest())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
-    p = subprocess.run([exe, path], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=env)
-    assert p.returncode == 0, p.stdout.decode(errors="replace")[-4000:]
-    assert b"%d lengths at 16 residues, 0 mismatches" % len(E.LENGTHS) in p.stdout
+    cases = struct.pack("<I", len(E.LENGTHS)) + b"".join(struct.pack("<I", n) + hashlib.sha256(E.message(n)).digest() for n in E.LENGTHS)
+    out = _emu.run_program(tmp_path, "emu_sha256.cpp", "EMU_SHA256_MAIN", cases)
+    assert "%d lengths at 16 residues, 0 mismatches" % len(E.LENGTHS) in out
