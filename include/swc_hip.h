@@ -322,7 +322,8 @@ int swc_lz4_multi_decompress(const uint8_t* in, size_t in_len, const uint8_t* di
 /* Host-side framing around the batch API (reference L3 "archives") */
 /* GzipArchive.unarchive(archive:) GzipArchive.swift:38-48 */
 int swc_gzip_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, size_t* out_len);
-/* GzipArchive.multiUnarchive(archive:) GzipArchive.swift:62-77; sizes[] splits *out per member */
+/* GzipArchive.multiUnarchive(archive:) GzipArchive.swift:62-77; sizes[] splits *out per member.  A BGZF file decodes in one launch; a
+ * file of plain members member by member, or -- swc_set_tuning "gzip_member_scan" = 1 -- from one launch over its candidate members */
 int swc_gzip_multi_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, size_t* out_len, size_t** sizes, size_t* n_members);
 /* ZlibArchive.unarchive(archive:) ZlibArchive.swift:25-42 */
 int swc_zlib_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, size_t* out_len);
@@ -378,15 +379,41 @@ int swc_unarchive_many_devices(int kind, const uint8_t* const* archives, const s
  *           decodes); aux = the dictionary-size byte | SWC_LZMA2_OPEN on all but the last; flags = 0.  A stream the walk cannot
  *           follow (a wrong control byte, a chunk past the end) is ONE unit and SWC_OK: its decode reports the error.  The units
  *           are candidates -- a match may reach behind a reset: a caller checks the result by the rule at swc_lzma2_aux.
+ *   kind 9  plain gzip members: every place a member MAY start, without a decode -- THE CANDIDATE RULE, which this kind states on the
+ *           host, csrc/gzip_scan.h on the device (swc_batch_gzip_index) and swc_gzip_multi_unarchive relies on ("gzip_member_scan").
+ *           Byte offset p of a buffer of len bytes is a candidate iff p + 20 <= len (10 header bytes, the 2-byte empty static block,
+ *           8 trailer bytes), in[p] == 0x1f, in[p+1] == 0x8b, in[p+2] == 0x08 and (in[p+3] & 0xE0) == 0 -- the magic, method and
+ *           reserved-flag tests of GzipHeader.swift:73-88 and nothing else; candidates may lie 3 bytes apart.  `next` of a candidate
+ *           is the offset of the candidate behind it, len for the last.  Its data position is p + 10, + 2 + XLEN with FEXTRA (the
+ *           sub-fields are not walked), + the zero-terminated FNAME and FCOMMENT where flagged -- each at most 256 bytes INCLUDING
+ *           its zero -- + 2 with FHCRC; every read in front of len.  One ref per candidate, in ascending order of p.  A usable ref
+ *           (flags bit 0 clear): offset = the data position, comp_len = next - offset - 8, uncomp_len = the little-endian 32-bit
+ *           word at next - 4 (the ISIZE the member has if the next candidate is where it ends), aux = offset - p.  A candidate
+ *           whose header leaves the buffer, whose name exceeds the limit (a condition, not a tuning: it bounds what one thread
+ *           reads of a hostile buffer; the walk decodes such a member) or whose data position + 10 > next is UNUSABLE: flags bit 0
+ *           set, offset = p, comp_len = uncomp_len = aux = 0.  Candidates are guesses -- the pattern occurs in names, in stored
+ *           data and in codes: a caller decodes the usable ones and keeps a result only where a sequential walk that starts at
+ *           offset 0 arrives at p, gzip_member_prepare puts the data where the ref did, the unit is SWC_OK with in_consumed ==
+ *           comp_len and uncomp_len bytes of output, and CRC-32 and ISIZE match (framing_deflate.cpp).
  * *n receives the number found; up to `cap` are written. */
 typedef struct swc_block_ref {
     uint64_t offset;      /* bytes from `in` (kind 5: bits) */
     uint64_t comp_len;
     uint64_t uncomp_len;  /* 0 = not known from the framing */
     uint32_t aux;
-    uint32_t flags;       /* kinds 4 and 7 only, else 0 */
+    uint32_t flags;       /* kinds 4, 7 and 9 only, else 0 */
 } swc_block_ref;
 int swc_index_blocks(int kind, const uint8_t* in, size_t len, swc_block_ref* refs, size_t cap, size_t* n);
+/* swc_index_blocks kind 9 for a buffer in HBM (csrc/gzip_scan.h: two passes over the buffer, a ref per candidate; an extension).  src,
+ * refs, n and workspace are DEVICE pointers; src and refs at any alignment.  *n receives the number of candidates found -- it may
+ * exceed cap; refs[0 .. min(*n, cap)) are written, each as an unlimited call writes it, and nothing behind them.  len == 0: *n = 0.
+ * The kernels run on opts->stream, and the call waits for them with opts->synchronize, as swc_batch_checksum does.
+ * SWC_E_INVALID_ARGUMENT: a null pointer (src with len != 0, refs with cap != 0, n, workspace); SWC_E_NEED_WORKSPACE: workspace_bytes
+ * is less than swc_gzip_index_workspace_bytes(len, cap), nothing is written; SWC_E_DEVICE.
+ *   swc_gzip_index_workspace_bytes  device scratch of that call: 12 bytes per 16 KiB of the buffer and 8 per ref that can be written */
+size_t swc_gzip_index_workspace_bytes(uint64_t len, uint64_t cap);
+int swc_batch_gzip_index(const uint8_t* src, uint64_t len, swc_block_ref* refs, uint64_t cap, uint64_t* n, void* workspace,
+                         size_t workspace_bytes, const swc_batch_opts* opts);
 
 /* ZipContainer.getEntryData (reference Sources/ZIP/ZipContainer.swift:61-118) for all entries of one container: every
  * entry is an independent stream whose location and sizes the caller already has from the central directory
@@ -489,6 +516,14 @@ const char* swc_version(void);
  *                               SWC_DEFLATE_LINKED as well, all but the first: they share the history of the units in front of them, so
  *                               streams whose units reach back (default pigz, Z_SYNC_FLUSH) decode as units instead of falling back;
  *                               0 (default): units that stand alone, as before;
+ *   "gzip_member_scan" = 0 | 1  process-wide: swc_gzip_multi_unarchive, for a file that is not BGZF, stages the file once, finds every
+ *                               place a member may start on the device (swc_index_blocks kind 9, csrc/gzip_scan.h), decodes the plausible
+ *                               candidates ahead in ONE launch and lets its sequential walk take from that launch every member that is
+ *                               exactly what the walk's own decode would have been accepted as (swc_stat "gzip_scan_members"); the walk
+ *                               decodes whatever else it meets itself (swc_stat "gzip_scan_walked"), so results, errors and partial
+ *                               results are the same.  A file with fewer than two candidates, or more than max(4096, len / 256), is
+ *                               walked as before.  0 (default): never -- it ships as 0; flipping it is a follow-up that cites
+ *                               profiles/gzip_members.txt;
  *   "lzma2_run_bytes" = n >= 0   process-wide: the LZMA2 decoders (swc_lzma2_decompress, swc_lzma2_decompress_data, the blocks of
  *                               swc_xz_unarchive / swc_xz_split_unarchive, swc_unarchive_many kinds 6 and 7, method 3 of
  *                               swc_7z_unpack_folders) cut a stream at its dictionary resets (swc_index_blocks kind 8) into units
@@ -519,7 +554,9 @@ int swc_last_phase_ms(float* ms, int cap);
  * .xz blocks the sequential walk took from the index-driven ahead-of-time batch, "deflate_unit_fallbacks" = Deflate streams that
  * were cut into units and had to be decoded whole after all, "sha256_device_units" = .xz blocks whose SHA-256 check the walk
  * took from the device, "lzma2_run_units" = the units of the LZMA2 streams that were cut at their dictionary resets and
- * accepted, "lzma2_run_fallbacks" = LZMA2 streams that were cut and had to be decoded whole after all.  Unknown key: -1. */
+ * accepted, "lzma2_run_fallbacks" = LZMA2 streams that were cut and had to be decoded whole after all, "gzip_scan_members" = members
+ * of plain multi-member gzip files that the walk took from the launch ahead ("gzip_member_scan"), "gzip_scan_walked" = members of
+ * such scanned files that the walk had to decode itself.  Unknown key: -1. */
 long long swc_stat(const char* key);
 
 #ifdef __cplusplus

@@ -284,3 +284,31 @@ def bgzf_archive(src, dst, block_size=65280, dynamic=False, workspace=None, dst_
                                     meta.data_ptr() + 8 if sizes else None, workspace.data_ptr(), int(workspace.numel()), C.byref(opts))
     host = meta.cpu().numpy().view(np.uint64)
     return st, int(host[0]), (host[1:] if sizes else None)
+
+
+def gzip_index_workspace_bytes(n_bytes, cap):
+    return _lib.load().swc_gzip_index_workspace_bytes(int(n_bytes), int(cap))
+
+
+def gzip_member_index(src, cap=None, workspace=None):
+    """Every place a plain gzip member may start in `src`, a torch uint8 tensor in HBM (`swc_batch_gzip_index`: the candidate rule of
+    include/swc_hip.h, swc_index_blocks kind 9).  cap: the most refs to write (default max(4096, bytes / 256)).  Returns (n, refs):
+    the number of candidates found -- it may exceed cap -- and the first min(n, cap) refs as an (m, 4) int64 tensor that stays on the
+    device: offset, comp_len, uncomp_len, and aux + (flags << 32) -- so a row whose last column is below 2^32 is usable (flags bit 0
+    clear), and offset / comp_len / uncomp_len are what a DeviceBatch("deflate", ...) unit over `src` takes."""
+    import torch
+    lib = _lib.load()
+    n_bytes = int(src.numel())
+    cap = max(4096, n_bytes // 256) if cap is None else int(cap)
+    if workspace is None:
+        workspace = torch.empty(max(gzip_index_workspace_bytes(n_bytes, cap), 16), dtype=torch.uint8, device=src.device)
+    refs = torch.empty((cap, 4), dtype=torch.int64, device=src.device)
+    n = torch.zeros(1, dtype=torch.int64, device=src.device)
+    dev = src.device
+    opts = _lib.SwcBatchOpts(dev.index if dev.index is not None else -1, torch.cuda.current_stream(dev).cuda_stream, 1, 0)
+    st = lib.swc_batch_gzip_index(src.data_ptr() if n_bytes else None, n_bytes, refs.data_ptr() if cap else None, cap, n.data_ptr(),
+                                  workspace.data_ptr(), int(workspace.numel()), C.byref(opts))
+    if st:
+        raise RuntimeError("swc_batch_gzip_index failed with status %d" % st)
+    found = int(n.item())
+    return found, refs[:min(found, cap)]

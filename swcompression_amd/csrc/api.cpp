@@ -279,6 +279,7 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
         std::vector<size_t> in_off(m), out_off(m), dict_off(m);
         // Host buffers are staged once: units that share a buffer (the bzip2 blocks of a stream) or that are sub-ranges of
         // one `base` buffer (the entries of a container, the members of a file) address the one staged copy.
+        // A base that is in HBM already (HostUnit::base_dev) is not staged: its units address it where it is.
         struct Staged { const uint8_t* p; size_t len, off; };
         std::vector<Staged> staged;
         std::map<std::pair<const uint8_t*, size_t>, size_t> seen;
@@ -289,10 +290,12 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
             const uint8_t* b = sub ? u.base : u.in;
             const size_t bl = sub ? u.base_len : u.in_len;
             auto key = std::make_pair(b, bl);
-            auto it = seen.find(key);
-            size_t at;
-            if (it != seen.end()) at = it->second;
-            else { at = in_total; seen[key] = at; staged.push_back(Staged{b, bl, at}); in_total += (bl + 15) & ~(size_t)15; }
+            size_t at = 0;   // (stays 0 for a base in HBM: Job::in is base_dev + (in - base), in_off goes unused)
+            if (!(sub && u.base_dev)) {
+                auto it = seen.find(key);
+                if (it != seen.end()) at = it->second;
+                else { at = in_total; seen[key] = at; staged.push_back(Staged{b, bl, at}); in_total += (bl + 15) & ~(size_t)15; }
+            }
             in_off[k] = at + (sub ? (size_t)(u.in - u.base) : 0);
             dict_off[k] = in_total;
             if (u.dict) in_total += (u.dict_len + 15) & ~(size_t)15;
@@ -350,7 +353,8 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
             const HostUnit& u = units[pending[k]];
             if (u.dict && u.dict_len) memcpy(up + dict_off[k], u.dict, u.dict_len);
             Job& j = jobs[k];
-            j.in = d_in + in_off[k];
+            const bool resident = u.base_dev && u.base && u.in >= u.base && u.in + u.in_len <= u.base + u.base_len;
+            j.in = resident ? u.base_dev + (u.in - u.base) : d_in + in_off[k];
             j.in_len = u.in_len;
             j.out = d_out + out_off[k];
             j.out_cap = cap[pending[k]];
@@ -519,6 +523,7 @@ int swc_set_tuning(const char* key, int value) try {
     if (!strcmp(key, "bzip2_team_walk") && value >= 0 && value <= 2) { set_bzip2_team_walk(value); return SWC_OK; }
     if (!strcmp(key, "bgzf_round_members") && value >= 1 && value <= 16384) { set_bgzf_round_members(value); return SWC_OK; }
     if (!strcmp(key, "deflate_unit_bytes") && value >= 0) { set_deflate_unit_bytes(value); return SWC_OK; }
+    if (!strcmp(key, "gzip_member_scan") && (value == 0 || value == 1)) { set_gzip_member_scan(value); return SWC_OK; }
     if (!strcmp(key, "lzma2_run_bytes") && value >= 0) { set_lzma2_run_bytes(value); return SWC_OK; }
     if (!strcmp(key, "deflate_units_linked") && (value == 0 || value == 1)) { set_deflate_units_linked(value); return SWC_OK; }
     if (!strcmp(key, "sha256_device_min_units") && value >= 1) { set_sha256_device_min_units(value); return SWC_OK; }
@@ -550,6 +555,8 @@ long long swc_stat(const char* key) {
     if (!strcmp(key, "sha256_device_units")) return g_stats[kStatSha256DeviceUnits].load();
     if (!strcmp(key, "lzma2_run_units")) return g_stats[kStatLzma2RunUnits].load();
     if (!strcmp(key, "lzma2_run_fallbacks")) return g_stats[kStatLzma2RunFallbacks].load();
+    if (!strcmp(key, "gzip_scan_members")) return g_stats[kStatGzipScanMembers].load();
+    if (!strcmp(key, "gzip_scan_walked")) return g_stats[kStatGzipScanWalked].load();
     return -1;
 }
 

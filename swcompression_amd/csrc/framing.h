@@ -43,6 +43,7 @@ int zlib_parse_header(const uint8_t* d, size_t n, size_t& pos);
 void set_deflate_unit_bytes(int v);   // "deflate_unit_bytes" (swc_set_tuning)
 void set_deflate_units_linked(int v); // "deflate_units_linked" (swc_set_tuning)
 void set_lzma2_run_bytes(int v);      // "lzma2_run_bytes" (swc_set_tuning)
+void set_gzip_member_scan(int v);     // "gzip_member_scan" (swc_set_tuning)
 void set_bgzf_round_members(int v);   // "bgzf_round_members" (swc_set_tuning): members per round of swc_bgzf_archive
 // many-archive batching helpers (framing_many.cpp)
 struct Lz4Plan {
@@ -67,6 +68,7 @@ void set_sha256_device_min_units(int v);   // "sha256_device_min_units" (swc_set
 int xz_run_many(const uint8_t* const* archives, const size_t* lens, size_t n, std::vector<int>& statuses, std::vector<std::vector<uint8_t>>& outs);
 // block discovery for swc_index_blocks (framing_many.cpp)
 bool bgzf_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out);
+void gzip_member_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out);
 void deflate_unit_index(const uint8_t* in, size_t in_len, size_t unit_bytes, std::vector<BlockRef64>& out);
 size_t deflate_unit_bytes();
 bool lz4_frame_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out);

@@ -15,6 +15,7 @@
 #include "framing.h"
 #include "launch.h"
 #include "bgzf_pack.h"
+#include "gzip_scan.h"
 
 namespace swc {
 
@@ -352,6 +353,128 @@ static bool bgzf_multi(const uint8_t* in, size_t in_len, uint8_t** all_out, size
     return true;
 }
 
+// ---- plain members, found ahead of the walk (csrc/gzip_scan.h) ---------------------------------------------------
+}  // extern "C"
+namespace swc {
+static std::atomic<int> g_gzip_member_scan{0};
+void set_gzip_member_scan(int v) { g_gzip_member_scan = v; }
+
+// The candidate rule of include/swc_hip.h (swc_index_blocks kind 9) on the host: what launch_gzip_index leaves on the device.
+void gzip_member_index(const uint8_t* in, size_t len, std::vector<BlockRef64>& out) {
+    if (len < 20) return;
+    std::vector<size_t> starts;
+    const uint8_t* const end = in + (len - 20) + 1;   // the first byte of a candidate lies in front of this
+    for (const uint8_t* p = in; p < end; p++) {
+        p = static_cast<const uint8_t*>(memchr(p, 0x1f, (size_t)(end - p)));
+        if (!p) break;
+        if (p[1] == 0x8b && p[2] == 0x08 && (p[3] & 0xE0) == 0) starts.push_back((size_t)(p - in));
+    }
+    for (size_t k = 0; k < starts.size(); k++) {
+        const size_t p = starts[k], next = k + 1 < starts.size() ? starts[k + 1] : len;
+        const uint32_t flags = in[p + 3];
+        size_t q = p + 10;
+        bool usable = true;
+        if (flags & 0x04) {
+            if (q + 2 > len) usable = false;
+            else q += 2 + ((size_t)in[q] | (size_t)in[q + 1] << 8);
+        }
+        for (uint32_t bit : {0x08u, 0x10u}) {
+            if (!usable || !(flags & bit)) continue;
+            const size_t room = q < len ? std::min<size_t>(256, len - q) : 0;
+            const uint8_t* z = room ? static_cast<const uint8_t*>(memchr(in + q, 0, room)) : nullptr;
+            if (!z) usable = false;
+            else q = (size_t)(z - in) + 1;
+        }
+        if (usable && (flags & 0x02)) q += 2;
+        if (usable && q + 10 <= next) {
+            const uint8_t* t = in + next - 4;
+            out.push_back({q, next - q - 8, (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24, (uint32_t)(q - p), 0});
+        } else out.push_back({p, 0, 0, 0, 1});
+    }
+}
+
+// The file staged once, indexed on the device, and every plausible candidate decoded in ONE launch into `all` (laid out by the
+// ISIZEs the candidates would have).  False: nothing to go by -- fewer than two candidates, more than a launch is worth, sizes no
+// file of this length has, no device memory -- and the walk decodes every member itself.
+struct ScanAhead {
+    std::vector<BlockRef64> refs;      // the plausible usable candidates, by offset
+    std::vector<HostUnit> units;       // units[k]: refs[k] decoded
+    uint8_t* all = nullptr;
+    size_t total = 0;
+    ~ScanAhead() { host_result_free(all); }
+};
+static bool gzip_scan_ahead(const uint8_t* in, size_t in_len, ScanAhead& s) {
+    if (in_len < 40 || !device_ready()) return false;
+    hipStream_t stream = hipStreamPerThread;
+    const uint64_t cap = std::max<uint64_t>(4096, in_len / 256);
+    const size_t ws_bytes = swc_gzip_index_workspace_bytes(in_len, cap);
+    DevBuf d_in(in_len + 16), d_refs(cap * sizeof(swc_block_ref) + sizeof(uint64_t)), d_ws(ws_bytes);
+    if (!d_in.ok() || !d_refs.ok() || !d_ws.ok()) return false;
+    uint8_t* up = pinned_stage(0, in_len);
+    if (up) memcpy(up, in, in_len);
+    uint64_t* d_n = reinterpret_cast<uint64_t*>(d_refs.u8() + cap * sizeof(swc_block_ref));
+    swc_batch_opts opts = {-1, stream, 0, 0};
+    uint64_t n = 0;
+    const bool issued = hipMemcpyAsync(d_in.ptr(), up ? up : in, in_len, hipMemcpyHostToDevice, stream) == hipSuccess &&
+                        swc_batch_gzip_index(d_in.u8(), in_len, reinterpret_cast<swc_block_ref*>(d_refs.ptr()), cap, d_n, d_ws.ptr(), ws_bytes, &opts) == SWC_OK &&
+                        hipMemcpyAsync(&n, d_n, sizeof n, hipMemcpyDeviceToHost, stream) == hipSuccess;
+    if (hipStreamSynchronize(stream) != hipSuccess || !issued) return false;   // (the staging buffer is the next call's again: nothing of this one in flight)
+    stat_add(kStatLaunches, 1);
+    if (n < 2 || n > cap) return false;   // (a file that dense in candidates is not worth a launch)
+    std::vector<swc_block_ref> found((size_t)n);
+    if (hipMemcpyAsync(found.data(), d_refs.ptr(), (size_t)n * sizeof(swc_block_ref), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess) return false;
+    for (const swc_block_ref& r : found) {
+        // (a ref is checked against the file before it is used: nothing the device says is trusted with an address)
+        if ((r.flags & 1) || r.comp_len < 2 || r.offset > in_len || r.comp_len > in_len - r.offset) continue;
+        if (r.uncomp_len > r.comp_len * 1100 + 4096) continue;   // (not a size this member can have: the walk decides)
+        s.refs.push_back({r.offset, r.comp_len, r.uncomp_len, r.aux, 0});
+        s.total += (size_t)r.uncomp_len;
+    }
+    if (s.refs.empty() || s.total > std::max<size_t>((size_t)64 << 20, in_len * 64)) return false;
+    s.all = host_result(s.total);
+    if (!s.all) return false;
+    s.units.resize(s.refs.size());
+    size_t o = 0;
+    for (size_t k = 0; k < s.refs.size(); k++) {
+        HostUnit& u = s.units[k];
+        u.in = in + s.refs[k].offset;
+        u.in_len = (size_t)s.refs[k].comp_len;
+        u.base = in;
+        u.base_len = in_len;
+        u.base_dev = d_in.u8();            // the copy the index read
+        u.sum_kind = 1;                    // CRC-32 on the device
+        u.cap_hint = std::max<size_t>((size_t)s.refs[k].uncomp_len, 64);
+        u.cap_exact = true;                // (a member of another size is the walk's)
+        u.dst = s.all + o;
+        u.dst_cap = (size_t)s.refs[k].uncomp_len;
+        o += u.dst_cap;
+    }
+    return run_units(SWC_CODEC_DEFLATE, s.units) == SWC_OK;
+}
+}  // namespace swc
+extern "C" {
+
+size_t swc_gzip_index_workspace_bytes(uint64_t len, uint64_t cap) { return (size_t)gzscan::plan(len, cap).bytes + 8; }   // (+ 8: cut from the first 8-byte boundary)
+
+int swc_batch_gzip_index(const uint8_t* src, uint64_t len, swc_block_ref* refs, uint64_t cap, uint64_t* n, void* workspace, size_t workspace_bytes,
+                         const swc_batch_opts* opts) try {
+    static_assert(sizeof(swc_block_ref) == sizeof(gzscan::Ref) && offsetof(swc_block_ref, flags) == offsetof(gzscan::Ref, flags), "layout");
+    if ((len && !src) || (cap && !refs) || !n || !workspace) return SWC_E_INVALID_ARGUMENT;
+    if (workspace_bytes < swc_gzip_index_workspace_bytes(len, cap)) return SWC_E_NEED_WORKSPACE;
+    if (!device_ready()) return SWC_E_DEVICE;
+    if (opts && opts->device >= 0 && hipSetDevice(opts->device) != hipSuccess) return SWC_E_DEVICE;
+    hipStream_t stream = opts ? static_cast<hipStream_t>(opts->stream) : nullptr;
+    uint8_t* ws = reinterpret_cast<uint8_t*>(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+    const hipError_t e = launch_gzip_index(src, len, refs, cap, n, ws, stream);
+    if (e == hipErrorInvalidValue) return SWC_E_INVALID_ARGUMENT;
+    if (e != hipSuccess) return SWC_E_DEVICE;
+    if (opts && opts->synchronize && hipStreamSynchronize(stream) != hipSuccess) return SWC_E_DEVICE;
+    return SWC_OK;
+} catch (...) {
+    return SWC_E_DEVICE;
+}
+
 int swc_gzip_multi_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, size_t* out_len, size_t** sizes, size_t* n_members) try {
     if (!out || !out_len || !sizes || !n_members || (in_len && !in)) return SWC_E_INVALID_ARGUMENT;
     {
@@ -365,11 +488,44 @@ int swc_gzip_multi_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, si
     // Plain multi-member gzip has no compressed-size field: member k+1 can only be located after
     // member k has been inflated, so members are discovered sequentially here.
     // (BGZF and many-archive batches go through swc_unarchive_many, which launches them together.)
+    // "gzip_member_scan" = 1: every place a member MAY start has been decoded ahead in one launch (gzip_scan_ahead); the walk below
+    // still meets the members one by one, and takes a member from that launch where it is, byte for byte, what the walk's own decode
+    // of it would have been checked to be.  Anything else is decoded here as ever: errors and partial results are this loop's.
     std::vector<uint8_t> all;
     std::vector<size_t> sz;
+    ScanAhead ahead;
+    const bool scanned = g_gzip_member_scan.load() != 0 && gzip_scan_ahead(in, in_len, ahead);
+    size_t ui = 0, taken = 0, taken_bytes = 0;
+    bool straight = scanned;   // the members so far are the units 0 .. taken - 1: ahead.all holds them as the result wants them
+    auto leave_straight = [&] {
+        if (straight) all.assign(ahead.all, ahead.all + taken_bytes);
+        straight = false;
+    };
     size_t pos = 0, walk_bound = (size_t)4 << 20;
     int st = SWC_OK;
     while (pos < in_len) {                                             // :66
+        if (scanned) {
+            auto start_of = [&](size_t k) { return (size_t)(ahead.refs[k].offset - ahead.refs[k].aux); };
+            while (ui < ahead.refs.size() && start_of(ui) < pos) ui++;   // (candidates inside the member in front)
+            if (ui < ahead.refs.size() && start_of(ui) == pos) {
+                const HostUnit& v = ahead.units[ui];
+                HostUnit tmp;
+                size_t next = 0;
+                bool bad_crc = false;
+                if (gzip_member_prepare(in, in_len, pos, tmp) == SWC_OK && tmp.in == v.in && v.status == SWC_OK && v.in_consumed == v.in_len && v.in_dst &&
+                    v.out_size == v.dst_cap && gzip_member_finish(in, in_len, (size_t)ahead.refs[ui].offset, v, next, bad_crc) == SWC_OK && !bad_crc) {
+                    if (ui != taken) leave_straight();
+                    if (straight) { taken++; taken_bytes += v.out_size; }
+                    else all.insert(all.end(), v.dst, v.dst + v.out_size);
+                    sz.push_back(v.out_size);
+                    stat_add(kStatGzipScanMembers, 1);
+                    pos = next;
+                    ui++;
+                    continue;
+                }
+            }
+            leave_straight();
+        }
         HostUnit u;
         st = gzip_member_prepare(in, in_len, pos, u);
         if (st) break;
@@ -377,6 +533,7 @@ int swc_gzip_multi_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, si
         const size_t data_pos = (size_t)(u.in - in);
         st = run_one_bounded(SWC_CODEC_DEFLATE, u, walk_bound, kCut);
         if (st) break;
+        if (scanned) stat_add(kStatGzipScanWalked, 1);
         walk_bound = std::max<size_t>(walk_bound, 4 * u.in_consumed + 65536);   // the next member is probably of this size
         bool crc_error;
         st = gzip_member_finish(in, in_len, data_pos, u, pos, crc_error);
@@ -385,8 +542,15 @@ int swc_gzip_multi_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, si
         sz.push_back(u.out.size());
         if (crc_error) { st = SWC_E_GZIP_WRONG_CRC; break; }           // :71-72 carries the members so far
     }
-    if (st != SWC_OK && st != SWC_E_GZIP_WRONG_CRC) { all.clear(); sz.clear(); }
-    give(all, out, out_len);
+    if (st != SWC_OK && st != SWC_E_GZIP_WRONG_CRC) { straight = false; all.clear(); sz.clear(); }
+    if (straight && taken == ahead.units.size()) {   // every unit was a member and nothing else was: the launch's buffer is the result
+        *out = ahead.all;
+        *out_len = ahead.total;
+        ahead.all = nullptr;
+    } else {
+        leave_straight();
+        give(all, out, out_len);
+    }
     *sizes = give_sizes(sz);
     *n_members = sz.size();
     return st;

@@ -469,6 +469,7 @@ int swc_index_blocks(int kind, const uint8_t* in, size_t len, swc_block_ref* ref
         case 5: bzip2_magic_index(in, len, v); break;
         case 6: xz_block_index(in, len, v); break;
         case 7: st = lzma2_chunk_index(in, len, v); break;
+        case 9: gzip_member_index(in, len, v); break;
         case 8: lzma2_unit_index(in, len, 1, len ? in[0] : (uint8_t)0, lzma2_run_bytes(), v); break;
         default: return SWC_E_INVALID_ARGUMENT;
     }

@@ -68,6 +68,8 @@ struct HostUnit {
     // ONCE and address their sub-range of it -- not each its own copy of everything behind its start.
     const uint8_t* base = nullptr;
     size_t base_len = 0;
+    // Optional: `base` is in HBM already, here (the caller keeps it until run_units returns): sub-ranges of it are not staged again
+    const uint8_t* base_dev = nullptr;
     size_t cap_hint = 0;         // 0 = use the codec's default policy
     bool cap_exact = false;      // cap_hint is authoritative (declared size): do not grow
     int32_t aux = 0;
@@ -130,7 +132,7 @@ struct Trace {
 
 // swc_stat counters (api.cpp), named as swc_stat's keys
 enum Stat { kStatLaunches, kStatUnits, kStatXzCacheHits, kStatDeflateUnitFallbacks, kStatSha256DeviceUnits, kStatLzma2RunUnits,
-            kStatLzma2RunFallbacks, kStatCount };
+            kStatLzma2RunFallbacks, kStatGzipScanMembers, kStatGzipScanWalked, kStatCount };
 void stat_add(Stat which, long long v);
 
 }  // namespace swc

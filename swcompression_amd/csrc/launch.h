@@ -35,6 +35,9 @@ hipError_t launch_deflate_compress_dynamic(Job* jobs, size_t n, hipStream_t stre
 // memory of bgzf::plan(len, bs).bytes, the Result at its plan().res; eof: the end-of-file member behind the last one
 hipError_t launch_bgzf_archive(const uint8_t* src, uint64_t len, uint32_t bs, bool dynamic, uint8_t* dst, uint64_t dst_cap, uint64_t* total,
                                uint64_t* sizes, uint8_t* ws, bool eof, hipStream_t stream);
+// gzip_scan.h: the candidate members of a buffer on `stream` (count, offsets, starts, refs); `ws`: 8-byte aligned device memory of
+// gzscan::plan(len, cap).bytes; *n (device) = the candidates found, refs (device, swc_block_ref) = the first min(*n, cap) of them
+hipError_t launch_gzip_index(const uint8_t* src, uint64_t len, void* refs, uint64_t cap, uint64_t* n, uint8_t* ws, hipStream_t stream);
 hipError_t launch_lzma(bool lzma2, Job* jobs, size_t n, void* spill, hipStream_t stream);
 size_t lzma_spill_bytes_per_job();
 hipError_t launch_bzip2(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStream_t stream);
