@@ -395,13 +395,24 @@ int swc_unarchive_many_devices(int kind, const uint8_t* const* archives, const s
  *           data and in codes: a caller decodes the usable ones and keeps a result only where a sequential walk that starts at
  *           offset 0 arrives at p, gzip_member_prepare puts the data where the ref did, the unit is SWC_OK with in_consumed ==
  *           comp_len and uncomp_len bytes of output, and CRC-32 and ISIZE match (framing_deflate.cpp).
+ *   kind 10 bzip2 marks: every place a block or the end of a stream MAY start, without a decode -- THE MARK RULE, which this kind
+ *           states on the host, csrc/bzip2_scan.h on the device (swc_batch_bzip2_index) and the bzip2 decoders rely on
+ *           ("bzip2_scan_bytes").  Bits are numbered MSB-first, as MsbBitReader reads them: bit k of the buffer is bit 7 - (k & 7) of
+ *           byte k >> 3; L = 8 * len.  Bit offset b is a mark iff b >= 32 (behind a stream header), b + 80 <= L, and the 48 bits from
+ *           b are 0x314159265359 (a block) or 0x177245385090 (the end of a stream).  The 80 bits are the magic and the 32-bit word
+ *           behind it: the walk (BZip2.swift:71) reports wrongMagic wherever fewer than 80 bits are left, before it looks at a block,
+ *           so a shorter candidate is never needed and there is no unusable form.  One ref per mark, in ascending order of b:
+ *           offset = b (bits, as kind 5), comp_len = next - b in bits, `next` the offset of the mark behind it and L for the last,
+ *           uncomp_len = 0, aux = the 32 bits at b + 48, MSB-first (a block's stored CRC, or the stream's combined CRC), flags bit 0
+ *           = the end of a stream.  Marks are candidates -- a magic may occur in data: a caller uses one only where a sequential
+ *           walk arrives at it, as with kind 5.  The block marks are exactly the kind-5 refs with offset + 80 <= L.
  * *n receives the number found; up to `cap` are written. */
 typedef struct swc_block_ref {
-    uint64_t offset;      /* bytes from `in` (kind 5: bits) */
+    uint64_t offset;      /* bytes from `in` (kinds 5 and 10: bits) */
     uint64_t comp_len;
     uint64_t uncomp_len;  /* 0 = not known from the framing */
     uint32_t aux;
-    uint32_t flags;       /* kinds 4, 7 and 9 only, else 0 */
+    uint32_t flags;       /* kinds 4, 7, 9 and 10 only, else 0 */
 } swc_block_ref;
 int swc_index_blocks(int kind, const uint8_t* in, size_t len, swc_block_ref* refs, size_t cap, size_t* n);
 /* swc_index_blocks kind 9 for a buffer in HBM (csrc/gzip_scan.h: two passes over the buffer, a ref per candidate; an extension).  src,
@@ -414,6 +425,18 @@ int swc_index_blocks(int kind, const uint8_t* in, size_t len, swc_block_ref* ref
 size_t swc_gzip_index_workspace_bytes(uint64_t len, uint64_t cap);
 int swc_batch_gzip_index(const uint8_t* src, uint64_t len, swc_block_ref* refs, uint64_t cap, uint64_t* n, void* workspace,
                          size_t workspace_bytes, const swc_batch_opts* opts);
+/* swc_index_blocks kind 10 for a buffer in HBM (csrc/bzip2_scan.h: one pass over the buffer, a second one over the 16 KiB tiles that
+ * hold marks, a ref per mark; an extension).  The contract is that of swc_batch_gzip_index: src, refs, n and workspace are DEVICE
+ * pointers; src and refs at any alignment.  *n receives the number of marks found -- it may exceed cap; refs[0 .. min(*n, cap)) are
+ * written, each as an unlimited call writes it, and nothing behind them.  len == 0: *n = 0.  The kernels run on opts->stream, and
+ * the call waits for them with opts->synchronize.  SWC_E_INVALID_ARGUMENT: a null pointer (src with len != 0, refs with cap != 0, n,
+ * workspace); SWC_E_NEED_WORKSPACE: workspace_bytes is less than swc_bzip2_index_workspace_bytes(len, cap), nothing is written;
+ * SWC_E_DEVICE.  A ref becomes a SWC_CODEC_BZIP2_BLOCK job over src: dict_len (the bit offset of the block's body) = offset + 80,
+ * dict (the stored CRC) = aux.
+ *   swc_bzip2_index_workspace_bytes  device scratch of that call: 12 bytes per 16 KiB of the buffer and 8 per ref that can be written */
+size_t swc_bzip2_index_workspace_bytes(uint64_t len, uint64_t cap);
+int swc_batch_bzip2_index(const uint8_t* src, uint64_t len, swc_block_ref* refs, uint64_t cap, uint64_t* n, void* workspace,
+                          size_t workspace_bytes, const swc_batch_opts* opts);
 
 /* ZipContainer.getEntryData (reference Sources/ZIP/ZipContainer.swift:61-118) for all entries of one container: every
  * entry is an independent stream whose location and sizes the caller already has from the central directory
@@ -524,6 +547,15 @@ const char* swc_version(void);
  *                               results are the same.  A file with fewer than two candidates, or more than max(4096, len / 256), is
  *                               walked as before.  0 (default): never -- it ships as 0; flipping it is a follow-up that cites
  *                               profiles/gzip_members.txt;
+ *   "bzip2_scan_bytes" = n >= 0   process-wide: the bzip2 decoders (swc_bzip2_decompress, swc_bzip2_multi_decompress,
+ *                               swc_unarchive_many / swc_unarchive_many_devices kind 5, the BZip2 entries of swc_zip_get_entries_data)
+ *                               stage an archive of at least n bytes once and find its marks on the device (swc_index_blocks kind 10,
+ *                               csrc/bzip2_scan.h) instead of scanning it on the host; every ref is checked against the host copy
+ *                               before it is used, the blocks are decoded from the staged copy, and the unchanged sequential walk
+ *                               decides, so results, errors and partial results are the same (swc_stat "bzip2_scan_files",
+ *                               "bzip2_scan_marks").  Room for max(4096, len / 4096) marks; a file with more is indexed once more with
+ *                               room for all.  Any device failure: the host scans.  0 (default): never -- it ships as 0; flipping
+ *                               it is a follow-up that cites profiles/bzip2_scan.txt;
  *   "lzma2_run_bytes" = n >= 0   process-wide: the LZMA2 decoders (swc_lzma2_decompress, swc_lzma2_decompress_data, the blocks of
  *                               swc_xz_unarchive / swc_xz_split_unarchive, swc_unarchive_many kinds 6 and 7, method 3 of
  *                               swc_7z_unpack_folders) cut a stream at its dictionary resets (swc_index_blocks kind 8) into units
@@ -556,7 +588,8 @@ int swc_last_phase_ms(float* ms, int cap);
  * took from the device, "lzma2_run_units" = the units of the LZMA2 streams that were cut at their dictionary resets and
  * accepted, "lzma2_run_fallbacks" = LZMA2 streams that were cut and had to be decoded whole after all, "gzip_scan_members" = members
  * of plain multi-member gzip files that the walk took from the launch ahead ("gzip_member_scan"), "gzip_scan_walked" = members of
- * such scanned files that the walk had to decode itself.  Unknown key: -1. */
+ * such scanned files that the walk had to decode itself, "bzip2_scan_files" = bzip2 archives whose marks the device found
+ * ("bzip2_scan_bytes"), "bzip2_scan_marks" = the block marks taken from it.  Unknown key: -1. */
 long long swc_stat(const char* key);
 
 #ifdef __cplusplus

@@ -417,15 +417,17 @@ class SwcBlockRef(C.Structure):
 
 def index_blocks(kind, data, flags=False):
     """Host block discovery (swc_index_blocks; no device needed).  kind: 'bgzf' | 'deflate' | 'lz4' | 'bzip2' | 'xz' | 'lzma2' |
-    'lzma2_runs' | 'gzip_members'.  Returns [(offset, comp_len, uncomp_len, aux)] -- for 'lzma2', and for any kind with flags=True, (offset, comp_len,
+    'lzma2_runs' | 'gzip_members' | 'bzip2_marks'.  Returns [(offset, comp_len, uncomp_len, aux)] -- for 'lzma2', and for any kind with flags=True, (offset, comp_len,
     uncomp_len, aux, flags): 'lz4' sets flags bit 0 on a block that continues its predecessor (a job with SWC_LZ4_LINKED);
     'deflate': the units a raw stream can be cut into behind its empty stored blocks (tuning value "deflate_unit_bytes"), aux = the
     DeviceBatch.DEFLATE_JOINED / DEFLATE_OPEN bits of the unit's job; 'lzma2_runs': the units a raw LZMA2 stream (first byte = the
     dictionary-size byte) can be cut into at its dictionary resets (tuning value "lzma2_run_bytes"), aux = the dictionary-size byte |
     DeviceBatch.LZMA2_OPEN on all but the last; 'gzip_members': every place a plain gzip member may start (the candidate rule of
     include/swc_hip.h, kind 9), aux = the length of its header, flags bit 0 = unusable (then offset is the candidate itself);
+    'bzip2_marks': every bit offset a block or the end of a stream may start at (the mark rule of include/swc_hip.h, kind 10),
+    comp_len = the bits to the next mark, aux = the 32 bits behind the magic, flags bit 0 = the end of a stream;
     offsets are bytes from the start (bzip2: bits)."""
-    kinds = {"bgzf": 1, "deflate": 3, "lz4": 4, "bzip2": 5, "xz": 6, "lzma2": 7, "lzma2_runs": 8, "gzip_members": 9}
+    kinds = {"bgzf": 1, "deflate": 3, "lz4": 4, "bzip2": 5, "xz": 6, "lzma2": 7, "lzma2_runs": 8, "gzip_members": 9, "bzip2_marks": 10}
     lib = _lib.load()
     data = bytes(data)
     n = C.c_size_t()

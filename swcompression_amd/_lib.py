@@ -98,6 +98,8 @@ def load():
     sig("swc_index_blocks", I, I, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, szp)
     sig("swc_gzip_index_workspace_bytes", C.c_size_t, C.c_uint64, C.c_uint64)
     sig("swc_batch_gzip_index", I, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SwcBatchOpts))
+    sig("swc_bzip2_index_workspace_bytes", C.c_size_t, C.c_uint64, C.c_uint64)
+    sig("swc_batch_bzip2_index", I, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SwcBatchOpts))
     sig("swc_unarchive_many", I, I, C.POINTER(C.c_char_p), szp, C.c_size_t, u8pp, szp, C.POINTER(C.c_int32))
     sig("swc_unarchive_many_devices", I, I, C.POINTER(C.c_char_p), szp, C.c_size_t, C.POINTER(C.c_int), C.c_size_t, u8pp, szp,
         C.POINTER(C.c_int32))

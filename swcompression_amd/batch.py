@@ -312,3 +312,33 @@ def gzip_member_index(src, cap=None, workspace=None):
         raise RuntimeError("swc_batch_gzip_index failed with status %d" % st)
     found = int(n.item())
     return found, refs[:min(found, cap)]
+
+
+def bzip2_index_workspace_bytes(n_bytes, cap):
+    return _lib.load().swc_bzip2_index_workspace_bytes(int(n_bytes), int(cap))
+
+
+def bzip2_mark_index(src, cap=None, workspace=None):
+    """Every bit offset a bzip2 block or the end of a stream may start at in `src`, a torch uint8 tensor in HBM
+    (`swc_batch_bzip2_index`: the mark rule of include/swc_hip.h, swc_index_blocks kind 10).  cap: the most refs to write (default
+    max(4096, bytes / 4096)).  Returns (n, refs): the number of marks found -- it may exceed cap -- and the first min(n, cap) refs as an
+    (m, 4) int64 tensor that stays on the device: offset and comp_len in bits, uncomp_len (0), and aux + (flags << 32) -- so a row
+    whose last column is below 2^32 is a block (flags bit 0 clear) and the column is its stored CRC.  Such a row is a
+    DeviceBatch("bzip2_block", ...) unit over the whole of `src`: extra = offset + 80 (the bit its body starts at), dict_value = aux.
+    Marks are candidates: a unit counts only where a sequential walk arrives at its offset."""
+    import torch
+    lib = _lib.load()
+    n_bytes = int(src.numel())
+    cap = max(4096, n_bytes // 4096) if cap is None else int(cap)
+    if workspace is None:
+        workspace = torch.empty(max(bzip2_index_workspace_bytes(n_bytes, cap), 16), dtype=torch.uint8, device=src.device)
+    refs = torch.empty((cap, 4), dtype=torch.int64, device=src.device)
+    n = torch.zeros(1, dtype=torch.int64, device=src.device)
+    dev = src.device
+    opts = _lib.SwcBatchOpts(dev.index if dev.index is not None else -1, torch.cuda.current_stream(dev).cuda_stream, 1, 0)
+    st = lib.swc_batch_bzip2_index(src.data_ptr() if n_bytes else None, n_bytes, refs.data_ptr() if cap else None, cap, n.data_ptr(),
+                                   workspace.data_ptr(), int(workspace.numel()), C.byref(opts))
+    if st:
+        raise RuntimeError("swc_batch_bzip2_index failed with status %d" % st)
+    found = int(n.item())
+    return found, refs[:min(found, cap)]

@@ -186,7 +186,7 @@ uint8_t* pinned_stage(int which, size_t n) {
 // A thread that staged a multi-gigabyte container once would hold that much page-locked memory until it ends: buffers above
 // the limit ("pinned_keep_mib") are released when the call that needed them is over (round-2 advisor; round 4: the limit was 256 MiB, and a
 // 268 MB BGZF file pinned its buffers again on every call).
-static void pinned_trim() {
+void pinned_trim() {
     for (int w = 0; w < 2; w++) (void)pinned_stage(w | 2, 0);
 }
 
@@ -524,6 +524,7 @@ int swc_set_tuning(const char* key, int value) try {
     if (!strcmp(key, "bgzf_round_members") && value >= 1 && value <= 16384) { set_bgzf_round_members(value); return SWC_OK; }
     if (!strcmp(key, "deflate_unit_bytes") && value >= 0) { set_deflate_unit_bytes(value); return SWC_OK; }
     if (!strcmp(key, "gzip_member_scan") && (value == 0 || value == 1)) { set_gzip_member_scan(value); return SWC_OK; }
+    if (!strcmp(key, "bzip2_scan_bytes") && value >= 0) { set_bzip2_scan_bytes(value); return SWC_OK; }
     if (!strcmp(key, "lzma2_run_bytes") && value >= 0) { set_lzma2_run_bytes(value); return SWC_OK; }
     if (!strcmp(key, "deflate_units_linked") && (value == 0 || value == 1)) { set_deflate_units_linked(value); return SWC_OK; }
     if (!strcmp(key, "sha256_device_min_units") && value >= 1) { set_sha256_device_min_units(value); return SWC_OK; }
@@ -557,6 +558,8 @@ long long swc_stat(const char* key) {
     if (!strcmp(key, "lzma2_run_fallbacks")) return g_stats[kStatLzma2RunFallbacks].load();
     if (!strcmp(key, "gzip_scan_members")) return g_stats[kStatGzipScanMembers].load();
     if (!strcmp(key, "gzip_scan_walked")) return g_stats[kStatGzipScanWalked].load();
+    if (!strcmp(key, "bzip2_scan_marks")) return g_stats[kStatBzip2ScanMarks].load();
+    if (!strcmp(key, "bzip2_scan_files")) return g_stats[kStatBzip2ScanFiles].load();
     return -1;
 }
 

@@ -1,6 +1,7 @@
 // framing.h -- host-side framing helpers shared between the C-ABI translation units.
 #ifndef SWC_FRAMING_H
 #define SWC_FRAMING_H
+#include <memory>
 #include <vector>
 #include "host_util.h"
 namespace swc {
@@ -44,6 +45,7 @@ void set_deflate_unit_bytes(int v);   // "deflate_unit_bytes" (swc_set_tuning)
 void set_deflate_units_linked(int v); // "deflate_units_linked" (swc_set_tuning)
 void set_lzma2_run_bytes(int v);      // "lzma2_run_bytes" (swc_set_tuning)
 void set_gzip_member_scan(int v);     // "gzip_member_scan" (swc_set_tuning)
+void set_bzip2_scan_bytes(int v);     // "bzip2_scan_bytes" (swc_set_tuning)
 void set_bgzf_round_members(int v);   // "bgzf_round_members" (swc_set_tuning): members per round of swc_bgzf_archive
 // many-archive batching helpers (framing_many.cpp)
 struct Lz4Plan {
@@ -58,7 +60,10 @@ struct Lz4Plan {
 };
 bool lz4_plan_prepare(const uint8_t* in, size_t n, Lz4Plan& plan, std::vector<HostUnit>& units);
 int lz4_plan_finish(const uint8_t* in, size_t n, const Lz4Plan& plan, const std::vector<HostUnit>& units, std::vector<uint8_t>& res);
-void bzip2_collect_candidates(const uint8_t* d, size_t n, std::vector<HostUnit>& units, std::vector<uint64_t>& used);
+// the copies in HBM of the archives whose marks the device found ("bzip2_scan_bytes"): the units of bzip2_collect_candidates address
+// them (HostUnit::base_dev), so one of these outlives the run_units call that decodes them
+struct Bzip2Staged { std::vector<std::unique_ptr<DevBuf>> files; };
+void bzip2_collect_candidates(const uint8_t* d, size_t n, std::vector<HostUnit>& units, std::vector<uint64_t>& used, Bzip2Staged& keep);
 int bzip2_finish_stream(const uint8_t* d, size_t n, std::vector<HostUnit>& units, size_t first_unit, const std::vector<uint64_t>& used,
                         std::vector<uint8_t>& res, size_t& byte_pos);
 size_t lzma2_announced_size(const uint8_t* p, size_t n);
@@ -73,6 +78,7 @@ void deflate_unit_index(const uint8_t* in, size_t in_len, size_t unit_bytes, std
 size_t deflate_unit_bytes();
 bool lz4_frame_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out);
 void bzip2_magic_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out);
+void bzip2_mark_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out);
 void xz_block_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out);
 int lzma2_chunk_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out);
 int lzma2_chunk_walk(const uint8_t* in, size_t in_len, size_t p, std::vector<BlockRef64>& out);

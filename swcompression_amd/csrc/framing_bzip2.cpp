@@ -9,11 +9,16 @@
 // arrives exactly at its bit offset, so false positives inside block data are simply never visited
 // and the outcome (bytes, error, error order) is identical to the sequential decoder.
 #include <algorithm>
+#include <atomic>
+#include <cstddef>
 #include <map>
+#include <memory>
 #include <thread>
 #include <system_error>
 #include <vector>
 #include "framing.h"
+#include "launch.h"
+#include "bzip2_scan.h"
 
 namespace swc {
 namespace {
@@ -34,6 +39,10 @@ inline uint64_t read_bits(const uint8_t* d, uint64_t bit, int count) {  // MSB-f
 // Discovery is the host's share of a bzip2 decode and must not be slower than the device: per BYTE position one big-endian
 // 64-bit window is compared against the magic at its eight bit alignments (48 + 7 bits fit), and large inputs are cut into
 // ranges scanned by several threads (a magic is found by the range that holds its first bit).
+// Ends: the magic of the end of a stream is looked for as well, and reported with kEndFound set in its offset (kind 10; without it
+// the loop is the one it was).
+constexpr uint64_t kEndFound = (uint64_t)1 << 63;
+template <bool Ends>
 void scan_range(const uint8_t* d, size_t n, size_t lo, size_t hi, uint64_t from_bit, std::vector<uint64_t>& out) {
     for (size_t i = lo; i < hi; i++) {
         if (i + 6 > n) break;                        // fewer than 48 bits left
@@ -41,13 +50,15 @@ void scan_range(const uint8_t* d, size_t n, size_t lo, size_t hi, uint64_t from_
         const size_t take = n - i < 8 ? n - i : 8;
         for (size_t k = 0; k < take; k++) v |= (uint64_t)d[i + k] << (56 - 8 * k);
         for (int s = 0; s < 8; s++) {
-            if (((v >> (16 - s)) & 0xFFFFFFFFFFFFull) != kBlockMagic) continue;
+            const uint64_t w = (v >> (16 - s)) & 0xFFFFFFFFFFFFull;
+            if (w != kBlockMagic && !(Ends && w == kEosMagic)) continue;
             if (s > 0 && i + 7 > n) continue;        // the last bits would lie past the end
             const uint64_t start = (uint64_t)i * 8 + (uint64_t)s;
-            if (start >= from_bit) out.push_back(start);
+            if (start >= from_bit) out.push_back(!Ends || w == kBlockMagic ? start : start | kEndFound);
         }
     }
 }
+template <bool Ends = false>
 void scan_block_magics(const uint8_t* d, size_t n, uint64_t from_bit, std::vector<uint64_t>& out) {
     if (n < 6) return;
     const size_t kMinPerThread = (size_t)4 << 20;
@@ -55,18 +66,18 @@ void scan_block_magics(const uint8_t* d, size_t n, uint64_t from_bit, std::vecto
     const size_t hw = std::thread::hardware_concurrency();
     if (threads > 16) threads = 16;
     if (hw && threads > hw) threads = hw;
-    if (threads < 2) { scan_range(d, n, 0, n, from_bit, out); return; }
+    if (threads < 2) { scan_range<Ends>(d, n, 0, n, from_bit, out); return; }
     std::vector<std::vector<uint64_t>> found(threads);
     std::vector<std::thread> pool;
     const size_t per = (n + threads - 1) / threads;
     size_t started = 0;
     try {
         for (size_t t = 0; t < threads; t++) {
-            pool.emplace_back([&, t] { scan_range(d, n, t * per, std::min(n, (t + 1) * per), from_bit, found[t]); });
+            pool.emplace_back([&, t] { scan_range<Ends>(d, n, t * per, std::min(n, (t + 1) * per), from_bit, found[t]); });
             started = t + 1;
         }
     } catch (const std::system_error&) {}   // no more threads to be had: this one scans the ranges nobody took
-    for (size_t t = started; t < threads; t++) scan_range(d, n, t * per, std::min(n, (t + 1) * per), from_bit, found[t]);
+    for (size_t t = started; t < threads; t++) scan_range<Ends>(d, n, t * per, std::min(n, (t + 1) * per), from_bit, found[t]);
     for (auto& th : pool) th.join();
     for (auto& f : found) out.insert(out.end(), f.begin(), f.end());
 }
@@ -124,10 +135,87 @@ void bzip2_magic_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>
     for (uint64_t c : cand) out.push_back({c, 0, 0, 0});
 }
 
-// Units for every candidate block of `d` (appended to `units`; `used` receives their bit offsets).
-void bzip2_collect_candidates(const uint8_t* d, size_t n, std::vector<HostUnit>& units, std::vector<uint64_t>& used) {
+// The marks of include/swc_hip.h (swc_index_blocks kind 10) on the host: what launch_bzip2_index leaves on the device.
+void bzip2_mark_index(const uint8_t* in, size_t in_len, std::vector<BlockRef64>& out) {
     std::vector<uint64_t> cand;
-    scan_block_magics(d, n, 32, cand);
+    scan_block_magics<true>(in, in_len, 32, cand);
+    const uint64_t total = (uint64_t)in_len * 8;
+    const size_t first = out.size();
+    for (uint64_t c : cand) {
+        const uint64_t b = c & ~kEndFound;
+        if (total - b < 80) continue;   // (the walk reports wrongMagic there before it looks)
+        if (out.size() > first) out.back().comp_len = b - out.back().offset;
+        out.push_back({b, total - b, 0, (uint32_t)read_bits(in, b + 48, 32), (c & kEndFound) ? 1u : 0u});
+    }
+}
+
+// ---- block marks found on the device (csrc/bzip2_scan.h) ---------------------------------------------------------
+static std::atomic<int> g_bzip2_scan_bytes{0};
+void set_bzip2_scan_bytes(int v) { g_bzip2_scan_bytes = v; }
+
+// The file staged once and indexed on the device: `cand` = the bit offsets of its block marks, every one checked against the host
+// copy; the staged copy joins `keep` (its units address it, HostUnit::base_dev).  False: no device memory, a failed call, a ref
+// that is not what the file says -- the host scans, and of this attempt only the launches it issued stay counted ("launches" counts
+// what ran).  Where no run_units call follows -- the attempt failed, or the file holds no block -- the pinned stage is trimmed here.
+static bool bzip2_scan_device(const uint8_t* d, size_t n, std::vector<uint64_t>& cand, Bzip2Staged& keep, const uint8_t*& staged) {
+    if (n < bzscan::kLeast || !device_ready()) return false;
+    hipStream_t stream = hipStreamPerThread;
+    std::unique_ptr<DevBuf> d_in(new DevBuf(n + 16));
+    if (!d_in->ok()) return false;
+    struct Trim { bool on = true; ~Trim() { if (on) pinned_trim(); } } trim;   // (runs after every synchronize below)
+    uint8_t* up = pinned_stage(0, n);
+    if (up) memcpy(up, d, n);
+    if (hipMemcpyAsync(d_in->ptr(), up ? up : d, n, hipMemcpyHostToDevice, stream) != hipSuccess) { (void)hipGetLastError(); return false; }
+    std::vector<swc_block_ref> found;
+    uint64_t cap = std::max<uint64_t>(4096, n / 4096);
+    for (int turn = 0;; turn++) {   // (a second turn for a file with more marks than the first had room for: there cap = what it counted)
+        const size_t ws_bytes = swc_bzip2_index_workspace_bytes(n, cap);
+        DevBuf d_refs(cap * sizeof(swc_block_ref) + sizeof(uint64_t)), d_ws(ws_bytes);
+        if (!d_refs.ok() || !d_ws.ok()) { (void)hipStreamSynchronize(stream); return false; }
+        uint64_t* d_n = reinterpret_cast<uint64_t*>(d_refs.u8() + cap * sizeof(swc_block_ref));
+        swc_batch_opts opts = {-1, stream, 0, 0};
+        uint64_t m = 0;
+        const bool issued = swc_batch_bzip2_index(d_in->u8(), n, reinterpret_cast<swc_block_ref*>(d_refs.ptr()), cap, d_n, d_ws.ptr(), ws_bytes, &opts) == SWC_OK &&
+                            hipMemcpyAsync(&m, d_n, sizeof m, hipMemcpyDeviceToHost, stream) == hipSuccess;
+        if (hipStreamSynchronize(stream) != hipSuccess || !issued) { (void)hipGetLastError(); return false; }   // (nothing of this call in flight any more)
+        stat_add(kStatLaunches, 1);
+        if (m > cap) {
+            if (turn || m > bzscan::most(n)) return false;
+            cap = m;
+            continue;
+        }
+        found.resize((size_t)m);
+        if (m && (hipMemcpyAsync(found.data(), d_refs.ptr(), (size_t)m * sizeof(swc_block_ref), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                  hipStreamSynchronize(stream) != hipSuccess)) { (void)hipGetLastError(); return false; }
+        break;
+    }
+    // (a ref is checked against the file before it is used: nothing the device says is trusted with an address)
+    const uint64_t total = (uint64_t)n * 8;
+    std::vector<uint64_t> blocks;
+    uint64_t behind = 32;   // the least offset the next ref may have
+    for (const swc_block_ref& r : found) {
+        if (r.offset < behind || r.offset > total - 80) return false;
+        const uint64_t magic = read_bits(d, r.offset, 48);
+        if (magic != ((r.flags & 1) ? kEosMagic : kBlockMagic)) return false;
+        behind = r.offset + 1;
+        if (!(r.flags & 1)) blocks.push_back(r.offset);
+    }
+    cand = std::move(blocks);
+    stat_add(kStatBzip2ScanFiles, 1);
+    stat_add(kStatBzip2ScanMarks, (long long)cand.size());
+    staged = d_in->u8();
+    keep.files.push_back(std::move(d_in));
+    trim.on = cand.empty();   // (units follow: run_units trims)
+    return true;
+}
+
+// Units for every candidate block of `d` (appended to `units`; `used` receives their bit offsets).  `keep`: the copy of the file in
+// HBM that the units address where the marks were found there ("bzip2_scan_bytes"); it lives until run_units has returned.
+void bzip2_collect_candidates(const uint8_t* d, size_t n, std::vector<HostUnit>& units, std::vector<uint64_t>& used, Bzip2Staged& keep) {
+    std::vector<uint64_t> cand;
+    const uint8_t* staged = nullptr;
+    const int least = g_bzip2_scan_bytes.load();
+    if (!(least > 0 && n >= (size_t)least && bzip2_scan_device(d, n, cand, keep, staged))) scan_block_magics(d, n, 32, cand);
     // first capacity of a block: what the stream header's level allows for the BWT column (level x 100,000 bytes,
     // BZip2+BlockSize.swift:11-33) -- the output is larger only where RLE1 runs expand, and such blocks are relaunched with
     // the size they report
@@ -137,6 +225,7 @@ void bzip2_collect_candidates(const uint8_t* d, size_t n, std::vector<HostUnit>&
         HostUnit u;
         u.in = d;
         u.in_len = n;
+        if (staged) { u.base = d; u.base_len = n; u.base_dev = staged; }         // the copy the index read: not staged again
         u.extra = c + 80;                                                         // bit offset of the block body
         u.dict_value = read_bits(d, c + 48, 32);                                  // stored block CRC
         u.cap_hint = std::min<size_t>(level * 100000 + 64, std::max<size_t>(4096, n * 64));
@@ -172,7 +261,8 @@ namespace {
 int decode_candidates(const uint8_t* d, size_t n, std::map<uint64_t, Decoded>& blocks) {
     std::vector<HostUnit> units;
     std::vector<uint64_t> used;
-    bzip2_collect_candidates(d, n, units, used);
+    Bzip2Staged keep;
+    bzip2_collect_candidates(d, n, units, used, keep);
     if (!units.empty()) {
         int st = run_units(SWC_CODEC_BZIP2_BLOCK, units);
         if (st) return st;
@@ -188,6 +278,26 @@ namespace swc { int bzip2_compress_device(const uint8_t* data, size_t len, int l
 using namespace swc;
 
 extern "C" {
+
+size_t swc_bzip2_index_workspace_bytes(uint64_t len, uint64_t cap) { return (size_t)bzscan::plan(len, cap).bytes + 8; }   // (+ 8: cut from the first 8-byte boundary)
+
+int swc_batch_bzip2_index(const uint8_t* src, uint64_t len, swc_block_ref* refs, uint64_t cap, uint64_t* n, void* workspace, size_t workspace_bytes,
+                          const swc_batch_opts* opts) try {
+    static_assert(sizeof(swc_block_ref) == sizeof(bzscan::Ref) && offsetof(swc_block_ref, flags) == offsetof(bzscan::Ref, flags), "layout");
+    if ((len && !src) || (cap && !refs) || !n || !workspace) return SWC_E_INVALID_ARGUMENT;
+    if (workspace_bytes < swc_bzip2_index_workspace_bytes(len, cap)) return SWC_E_NEED_WORKSPACE;
+    if (!device_ready()) return SWC_E_DEVICE;
+    if (opts && opts->device >= 0 && hipSetDevice(opts->device) != hipSuccess) return SWC_E_DEVICE;
+    hipStream_t stream = opts ? static_cast<hipStream_t>(opts->stream) : nullptr;
+    uint8_t* ws = reinterpret_cast<uint8_t*>(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+    const hipError_t e = launch_bzip2_index(src, len, refs, cap, n, ws, stream);
+    if (e == hipErrorInvalidValue) return SWC_E_INVALID_ARGUMENT;
+    if (e != hipSuccess) return SWC_E_DEVICE;
+    if (opts && opts->synchronize && hipStreamSynchronize(stream) != hipSuccess) return SWC_E_DEVICE;
+    return SWC_OK;
+} catch (...) {
+    return SWC_E_DEVICE;
+}
 
 int swc_bzip2_decompress(const uint8_t* in, size_t in_len, uint8_t** out, size_t* out_len, size_t* in_consumed) try {
     if (!out || !out_len || (in_len && !in)) return SWC_E_INVALID_ARGUMENT;

@@ -125,9 +125,10 @@ int many_bzip2(const uint8_t* const* archives, const size_t* lens, size_t n, std
     std::vector<HostUnit> units;
     std::vector<std::vector<uint64_t>> used(n);
     std::vector<size_t> first(n);
+    Bzip2Staged keep;   // (the archives indexed on the device stay in HBM until the launch below has read them)
     for (size_t i = 0; i < n; i++) {
         first[i] = units.size();
-        bzip2_collect_candidates(archives[i], lens[i], units, used[i]);
+        bzip2_collect_candidates(archives[i], lens[i], units, used[i], keep);
     }
     if (!units.empty()) {
         int st = run_units(SWC_CODEC_BZIP2_BLOCK, units);
@@ -470,6 +471,7 @@ int swc_index_blocks(int kind, const uint8_t* in, size_t len, swc_block_ref* ref
         case 6: xz_block_index(in, len, v); break;
         case 7: st = lzma2_chunk_index(in, len, v); break;
         case 9: gzip_member_index(in, len, v); break;
+        case 10: bzip2_mark_index(in, len, v); break;
         case 8: lzma2_unit_index(in, len, 1, len ? in[0] : (uint8_t)0, lzma2_run_bytes(), v); break;
         default: return SWC_E_INVALID_ARGUMENT;
     }

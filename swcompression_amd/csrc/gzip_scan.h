@@ -115,7 +115,8 @@ SWC_D void count_tile(uint64_t tile, const uint8_t* src, uint64_t len, uint32_t*
     SIMT_END
 }
 
-// ---- offsets: ONE wavefront, 64 tiles per step (a step's sum stays far below 2^32: 64 x kTile / 3) -----------------------------------
+// ---- offsets: ONE wavefront, 64 tiles per step.  Two users: the candidates here and the marks of bzip2_scan.h; a step's sum stays far
+// below 2^32 for both (64 x kTile / 3 candidates, 64 x 8 x kTile = 2^23 marks) ---------------------------------------------------------
 template <int N>
 SWC_D void scan_tiles(const uint32_t* counts, uint64_t n_tiles, uint64_t* prefix, uint64_t* n) {
     using namespace simt;

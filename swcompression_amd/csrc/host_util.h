@@ -48,6 +48,9 @@ private:
 // Page-locked host staging memory of the calling thread, kept between calls (pageable hipMemcpy was most of a small
 // single-shot call).  nullptr if the allocation fails (the caller falls back to its own pageable buffer).
 uint8_t* pinned_stage(int which, size_t n);
+// A staging buffer above "pinned_keep_mib" goes back when the call that needed it is over: run_units does this itself; a call that
+// staged something and never reaches run_units does it here
+void pinned_trim();
 
 // Host result handed to the caller (released with swc_free).  Large results come from -- and go back to -- a small cache
 // of buffers whose pages are already mapped (api.cpp): a fresh 268 MB allocation costs more in page faults (24 ms) than the
@@ -132,7 +135,8 @@ struct Trace {
 
 // swc_stat counters (api.cpp), named as swc_stat's keys
 enum Stat { kStatLaunches, kStatUnits, kStatXzCacheHits, kStatDeflateUnitFallbacks, kStatSha256DeviceUnits, kStatLzma2RunUnits,
-            kStatLzma2RunFallbacks, kStatGzipScanMembers, kStatGzipScanWalked, kStatCount };
+            kStatLzma2RunFallbacks, kStatGzipScanMembers, kStatGzipScanWalked, kStatBzip2ScanMarks,
+            kStatBzip2ScanFiles, kStatCount };
 void stat_add(Stat which, long long v);
 
 }  // namespace swc

@@ -24,6 +24,7 @@
 #include "delta_group.h"
 #include "bgzf_pack.h"
 #include "gzip_scan.h"
+#include "bzip2_scan.h"
 #include "launch.h"
 
 namespace swc {
@@ -739,6 +740,34 @@ hipError_t launch_gzip_index(const uint8_t* src, uint64_t len, void* refs, uint6
     if (n_tiles) hipLaunchKernelGGL(swc_gzip_write_kernel, dim3((unsigned)n_tiles), dim3(kWave), 0, stream, src, len, prefix, starts, p.slots);
     if (threads) hipLaunchKernelGGL(swc_gzip_refs_kernel, dim3((unsigned)((threads + kWave - 1) / kWave)), dim3(kWave), 0, stream, src, len, starts, n, cap,
                                     static_cast<gzscan::Ref*>(refs));
+    return hipGetLastError();
+}
+
+// ---- bzip2 marks (bzip2_scan.h): count per tile | offsets (the gzip index's kernel) | starts per tile | a ref per mark ------------------
+__global__ __launch_bounds__(64) void swc_bzip2_count_kernel(const uint8_t* __restrict__ src, uint64_t len, uint32_t* __restrict__ counts) {
+    bzscan::count_tile<kWave>(blockIdx.x, src, len, counts);
+}
+__global__ __launch_bounds__(64) void swc_bzip2_write_kernel(const uint8_t* __restrict__ src, uint64_t len, const uint32_t* __restrict__ counts,
+                                                             const uint64_t* __restrict__ prefix, uint64_t* __restrict__ starts, uint64_t slots) {
+    bzscan::write_tile<kWave>(blockIdx.x, src, len, counts, prefix, starts, slots);
+}
+__global__ __launch_bounds__(64) void swc_bzip2_refs_kernel(const uint8_t* __restrict__ src, uint64_t len, const uint64_t* __restrict__ starts, const uint64_t* __restrict__ n,
+                                                            uint64_t cap, bzscan::Ref* __restrict__ refs) {
+    bzscan::mark_refs<kWave>(blockIdx.x, src, len, starts, n, cap, refs);
+}
+// `ws`: 8-byte aligned, bzscan::plan(len, cap).bytes of it.  *n: the marks found; refs[0 .. min(*n, cap)) are written.
+hipError_t launch_bzip2_index(const uint8_t* src, uint64_t len, void* refs, uint64_t cap, uint64_t* n, uint8_t* ws, hipStream_t stream) {
+    const bzscan::Plan p = bzscan::plan(len, cap);
+    const uint64_t n_tiles = bzscan::tiles(len, (uint32_t)((uintptr_t)src & 15u)), threads = p.slots - 1;
+    if (n_tiles >= 0x7FFFFFFFull || (threads + kWave - 1) / kWave >= 0x7FFFFFFFull) return hipErrorInvalidValue;
+    uint64_t* prefix = reinterpret_cast<uint64_t*>(ws + p.prefix);
+    uint64_t* starts = reinterpret_cast<uint64_t*>(ws + p.starts);
+    uint32_t* counts = reinterpret_cast<uint32_t*>(ws + p.counts);
+    if (n_tiles) hipLaunchKernelGGL(swc_bzip2_count_kernel, dim3((unsigned)n_tiles), dim3(kWave), 0, stream, src, len, counts);
+    hipLaunchKernelGGL(swc_gzip_scan_kernel, dim3(1), dim3(kWave), 0, stream, counts, n_tiles, prefix, n);
+    if (n_tiles) hipLaunchKernelGGL(swc_bzip2_write_kernel, dim3((unsigned)n_tiles), dim3(kWave), 0, stream, src, len, counts, prefix, starts, p.slots);
+    if (threads) hipLaunchKernelGGL(swc_bzip2_refs_kernel, dim3((unsigned)((threads + kWave - 1) / kWave)), dim3(kWave), 0, stream, src, len, starts, n, cap,
+                                    static_cast<bzscan::Ref*>(refs));
     return hipGetLastError();
 }
 

@@ -38,6 +38,9 @@ hipError_t launch_bgzf_archive(const uint8_t* src, uint64_t len, uint32_t bs, bo
 // gzip_scan.h: the candidate members of a buffer on `stream` (count, offsets, starts, refs); `ws`: 8-byte aligned device memory of
 // gzscan::plan(len, cap).bytes; *n (device) = the candidates found, refs (device, swc_block_ref) = the first min(*n, cap) of them
 hipError_t launch_gzip_index(const uint8_t* src, uint64_t len, void* refs, uint64_t cap, uint64_t* n, uint8_t* ws, hipStream_t stream);
+// bzip2_scan.h: the marks of a buffer (block and end-of-stream magics at any bit) on `stream`, as launch_gzip_index; `ws`: 8-byte aligned
+// device memory of bzscan::plan(len, cap).bytes
+hipError_t launch_bzip2_index(const uint8_t* src, uint64_t len, void* refs, uint64_t cap, uint64_t* n, uint8_t* ws, hipStream_t stream);
 hipError_t launch_lzma(bool lzma2, Job* jobs, size_t n, void* spill, hipStream_t stream);
 size_t lzma_spill_bytes_per_job();
 hipError_t launch_bzip2(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStream_t stream);
