@@ -334,7 +334,9 @@ int swc_xz_split_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, size
 /* Many independent archives in one call: host-side block discovery + ONE batched launch.
  * archives[i]/lens[i] are host buffers; outs[i]/out_lens[i]/statuses[i] are filled per archive
  * (outs[i] released with swc_free).  kind: 1 = gzip member (incl. BGZF), 2 = zlib stream,
- * 3 = raw deflate, 4 = LZ4 frame, 5 = bzip2 stream, 6 = xz stream, 7 = raw LZMA2 (first byte = dict byte). */
+ * 3 = raw deflate, 4 = LZ4 frame, 5 = bzip2 stream, 6 = xz stream, 7 = raw LZMA2 (first byte = dict byte).
+ * An archive that fails in its header -- before the reference would decode any payload -- contributes nothing to the launch, as in
+ * the single-shot calls: a set of nothing but such archives is answered without a device; any other set returns SWC_E_DEVICE there. */
 int swc_unarchive_many(int kind, const uint8_t* const* archives, const size_t* lens, size_t n,
                        uint8_t** outs, size_t* out_lens, int32_t* statuses);
 /* The same over several GPUs of one node (the reference has no counterpart: its callers loop over archives on one core).

@@ -104,7 +104,7 @@ int refcpu_gzip_multi_unarchive(const uint8_t* in, size_t in_len, uint8_t** out,
         int crc_error;
         size_t start = b.len;
         st = gzip_member(&r, &b, &crc_error);
-        if (st) break;
+        if (st) { b.len = 0; n = 0; break; } /* only wrongCRC carries the members so far (:73) */
         if (n == cap) { cap *= 2; sizes = (size_t*)realloc(sizes, cap * sizeof(size_t)); }
         sizes[n++] = b.len - start;
         if (crc_error) { st = SWC_E_GZIP_WRONG_CRC; break; } /* :71-72 carries members so far incl. this one */

@@ -241,7 +241,7 @@ int refcpu_lz4_multi_decompress(const uint8_t* in, size_t in_len, const uint8_t*
     size_t pos = 0;
     int have_dict = dict != NULL;
     do {
-        if (pos + 4 > in_len) { st = SWC_E_DATA_TRUNCATED; break; } /* :123 */
+        if (pos + 4 > in_len) { st = SWC_E_DATA_TRUNCATED; b.len = 0; nf = 0; break; } /* :123 (carries nothing) */
         uint32_t magic = (uint32_t)in[pos] | (uint32_t)in[pos + 1] << 8 | (uint32_t)in[pos + 2] << 16 | (uint32_t)in[pos + 3] << 24;
         pos += 4;
         size_t adv = 0, start = b.len;

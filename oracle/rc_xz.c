@@ -270,7 +270,7 @@ static int xz_run(const uint8_t* in, size_t in_len, rc_buf* b, size_t** sizes_ou
     size_t* sizes = (size_t*)malloc(cap * sizeof(size_t));
     int st = SWC_OK;
     while (!rc_b_finished(&r)) {
-        if (rc_b_left(&r) < 32) { st = SWC_E_XZ_WRONG_MAGIC; break; } /* :37 */
+        if (rc_b_left(&r) < 32) { st = SWC_E_XZ_WRONG_MAGIC; b->len = 0; n = 0; break; } /* :39 (carries nothing, like every error but wrongCheck) */
         int check_error;
         size_t start = b->len;
         st = xz_stream(&r, b, &check_error);

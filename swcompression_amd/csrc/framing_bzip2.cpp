@@ -90,14 +90,20 @@ struct Decoded {
 
 // decompress(_:) BZip2.swift:50-95 replayed over pre-decoded blocks.  `byte_pos` is the aligned start of
 // the stream; on return it is the aligned position just past the stream (callers align(), :45).
+// The four bytes in front of the blocks (:53-66): what the walk answers before it looks at a block, or SWC_OK.
+int stream_header(const uint8_t* d, size_t n, size_t byte_pos) {
+    if ((uint64_t)n * 8 - (uint64_t)byte_pos * 8 < 32) return SWC_E_BZIP2_WRONG_MAGIC;        // :53
+    if (!(d[byte_pos] == 0x42 && d[byte_pos + 1] == 0x5A)) return SWC_E_BZIP2_WRONG_MAGIC;   // "BZ" :59-60
+    if (d[byte_pos + 2] != 104) return SWC_E_BZIP2_WRONG_VERSION;                  // 'h' :62-63
+    if (d[byte_pos + 3] < 0x31 || d[byte_pos + 3] > 0x39) return SWC_E_BZIP2_WRONG_BLOCK_SIZE;  // :65-66
+    return SWC_OK;
+}
+
 int walk_stream(const uint8_t* d, size_t n, size_t& byte_pos, const std::map<uint64_t, Decoded>& blocks,
                 std::vector<uint8_t>& out) {
     const uint64_t total = (uint64_t)n * 8;
     uint64_t cur = (uint64_t)byte_pos * 8;
-    if (total - cur < 32) return SWC_E_BZIP2_WRONG_MAGIC;                         // :53
-    if (!(d[byte_pos] == 0x42 && d[byte_pos + 1] == 0x5A)) return SWC_E_BZIP2_WRONG_MAGIC;   // "BZ" :59-60
-    if (d[byte_pos + 2] != 104) return SWC_E_BZIP2_WRONG_VERSION;                  // 'h' :62-63
-    if (d[byte_pos + 3] < 0x31 || d[byte_pos + 3] > 0x39) return SWC_E_BZIP2_WRONG_BLOCK_SIZE;  // :65-66
+    if (const int st = stream_header(d, n, byte_pos)) return st;
     cur += 32;
     uint32_t total_crc = 0;
     for (;;) {
@@ -212,6 +218,7 @@ static bool bzip2_scan_device(const uint8_t* d, size_t n, std::vector<uint64_t>&
 // Units for every candidate block of `d` (appended to `units`; `used` receives their bit offsets).  `keep`: the copy of the file in
 // HBM that the units address where the marks were found there ("bzip2_scan_bytes"); it lives until run_units has returned.
 void bzip2_collect_candidates(const uint8_t* d, size_t n, std::vector<HostUnit>& units, std::vector<uint64_t>& used, Bzip2Staged& keep) {
+    if (stream_header(d, n, 0) != SWC_OK) return;   // (the walk stops in front of the first block: no candidate is ever visited, and the answer needs no device)
     std::vector<uint64_t> cand;
     const uint8_t* staged = nullptr;
     const int least = g_bzip2_scan_bytes.load();

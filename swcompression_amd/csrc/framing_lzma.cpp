@@ -126,20 +126,25 @@ int xz_sum_kind(int check_type, size_t units) {
 }
 typedef std::map<int64_t, Predecoded> BlockCache;
 
-// XZBlock.init (XZBlock.swift:18-97).  Appends the block's data to `out`.
-int xz_block(uint32_t header_size_byte, Reader& r, int check_size, std::vector<uint8_t>& out, int64_t& unpadded_size,
-             int64_t& uncomp_size, BlockCache* cache, BlockSum* bsum = nullptr) {
+// The header of a block (XZBlock.swift:19-75), read from behind its size byte; leaves `r` at the block's data.  Decodes nothing.
+struct BlockHeader {
+    int64_t start = 0, compressed_size = -1, uncompressed_size = -1;
+    int filters_count = 0;
+    Filter filters[4];
+};
+int xz_block_header(uint32_t header_size_byte, Reader& r, BlockHeader& h) {
     int st;
-    const int64_t header_start = r.off - 1;
+    const int64_t header_start = h.start = r.off - 1;
     const int64_t real_header_size = ((int64_t)header_size_byte + 1) * 4;
     const uint32_t flags = r.u8();
     if (r.trap) return SWC_E_REF_TRAP;
-    const int filters_count = (int)(flags & 0x03) + 1;
+    const int filters_count = h.filters_count = (int)(flags & 0x03) + 1;
     if (flags & 0x3C) return SWC_E_XZ_WRONG_FIELD;                                // :27
-    int64_t compressed_size = -1, uncompressed_size = -1;
+    int64_t& compressed_size = h.compressed_size;
+    int64_t& uncompressed_size = h.uncompressed_size;
     if (flags & 0x40) { if ((st = multibyte(r, compressed_size))) return st; }
     if (flags & 0x80) { if ((st = multibyte(r, uncompressed_size))) return st; }
-    Filter filters[4];
+    Filter* const filters = h.filters;
     for (int i = 0; i < filters_count; i++) {
         int64_t id, ps;
         if ((st = multibyte(r, id))) return st;
@@ -167,6 +172,18 @@ int xz_block(uint32_t header_size_byte, Reader& r, int check_size, std::vector<u
     if (header_start < 0 || header_start + real_header_size - 4 > (int64_t)r.n) return SWC_E_REF_TRAP;
     if (swc_crc32(r.d + header_start, (size_t)(real_header_size - 4), 0) != hcrc) return SWC_E_XZ_WRONG_INFO_CRC;
     r.off = header_start + real_header_size;
+    return SWC_OK;
+}
+
+// XZBlock.init (XZBlock.swift:18-97).  Appends the block's data to `out`.
+int xz_block(uint32_t header_size_byte, Reader& r, int check_size, std::vector<uint8_t>& out, int64_t& unpadded_size,
+             int64_t& uncomp_size, BlockCache* cache, BlockSum* bsum = nullptr) {
+    BlockHeader h;
+    int st = xz_block_header(header_size_byte, r, h);
+    if (st) return st;
+    const int64_t header_start = h.start, compressed_size = h.compressed_size, uncompressed_size = h.uncompressed_size;
+    const int filters_count = h.filters_count;
+    const Filter* const filters = h.filters;
 
     const int64_t data_start = r.off;
     // :78 filters.reversed().reduce(byteReader): the last filter reads the archive, earlier ones its output
@@ -218,10 +235,9 @@ int xz_block(uint32_t header_size_byte, Reader& r, int check_size, std::vector<u
     return SWC_OK;
 }
 
-// processStream (XZArchive.swift:90-130)
-int xz_stream(Reader& r, std::vector<uint8_t>& out, bool& check_error, BlockCache* cache) {
+// XZStreamHeader.init (XZStreamHeader.swift:33-57)
+int xz_stream_header(Reader& r, int& check_type, int& check_size) {
     static const uint8_t magic[6] = {0xFD, 0x37, 0x7A, 0x58, 0x5A, 0x00};
-    check_error = false;
     if (r.left() < 12) return SWC_E_REF_TRAP;
     if (memcmp(r.d + r.off, magic, 6) != 0) return SWC_E_XZ_WRONG_MAGIC;         // XZStreamHeader.swift:35
     r.off += 6;
@@ -230,8 +246,7 @@ int xz_stream(Reader& r, std::vector<uint8_t>& out, bool& check_error, BlockCach
     const uint8_t fb[2] = {f0, f1};
     if (swc_crc32(fb, 2, 0) != fcrc) return SWC_E_XZ_WRONG_INFO_CRC;
     if (!(f0 == 0 && (f1 & 0xF0) == 0)) return SWC_E_XZ_WRONG_FIELD;
-    const int check_type = f1 & 0x0F;
-    int check_size;
+    check_type = f1 & 0x0F;
     switch (check_type) {
         case 0x00: check_size = 0; break;
         case 0x01: check_size = 4; break;
@@ -239,9 +254,33 @@ int xz_stream(Reader& r, std::vector<uint8_t>& out, bool& check_error, BlockCach
         case 0x0A: check_size = 32; break;
         default: return SWC_E_XZ_WRONG_FIELD;
     }
+    return SWC_OK;
+}
+
+// What the walk answers before it decodes anything: the archive's length (XZArchive.swift:39), the header of its first stream and of
+// that stream's first block.  SWC_OK: nothing wrong that far.  An archive that fails here has no block decoded ahead, and its
+// answer needs no device.
+int xz_head_status(const uint8_t* d, size_t n) {
+    Reader r{d, n, 0, false};
+    if (r.finished()) return SWC_OK;
+    if (r.left() < 32) return SWC_E_XZ_WRONG_MAGIC;
+    int check_type, check_size;
+    int st = xz_stream_header(r, check_type, check_size);
+    if (st) return st;
+    const uint32_t hs = r.u8();
+    if (hs == 0) return SWC_OK;   // (no block: the index)
+    BlockHeader h;
+    return xz_block_header(hs, r, h);
+}
+
+// processStream (XZArchive.swift:90-130)
+int xz_stream(Reader& r, std::vector<uint8_t>& out, bool& check_error, BlockCache* cache) {
+    check_error = false;
+    int check_type, check_size;
+    int st = xz_stream_header(r, check_type, check_size);
+    if (st) return st;
     std::vector<std::pair<int64_t, int64_t>> infos;
     int64_t index_size = -1;
-    int st;
     for (;;) {
         const uint32_t hs = r.u8();
         if (r.trap) return SWC_E_REF_TRAP;
@@ -410,6 +449,7 @@ void xz_cache_fill(const std::vector<Cand>& cands, std::vector<HostUnit>& units,
 
 void xz_predecode(const uint8_t* d, size_t n, BlockCache& cache) {
     std::vector<Cand> cands;
+    if (xz_head_status(d, n) != SWC_OK) return;   // (the walk stops before its first decode: nothing to decode ahead)
     xz_candidates(d, n, cands);
     if (cands.size() < 2) return;            // a single block gains nothing from being decoded ahead
     // the blocks' check, if the streams of the archive agree on it: on the device, behind the decode (a launch computes one kind;
@@ -474,7 +514,7 @@ int xz_run_many(const uint8_t* const* archives, const size_t* lens, size_t n, st
     std::vector<std::vector<Cand>> cands(n);
     size_t total = 0, by_type[16] = {0};
     for (size_t i = 0; i < n; i++) {
-        xz_candidates(archives[i], lens[i], cands[i]);
+        if (xz_head_status(archives[i], lens[i]) == SWC_OK) xz_candidates(archives[i], lens[i], cands[i]);   // (else the walk's answer needs no decode)
         total += cands[i].size();
         for (const Cand& c : cands[i]) by_type[c.check_type & 15]++;
     }

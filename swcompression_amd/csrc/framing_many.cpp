@@ -247,7 +247,8 @@ int swc_unarchive_many(int kind, const uint8_t* const* archives, const size_t* l
                        uint8_t** outs, size_t* out_lens, int32_t* statuses) try {
     if (kind < 1 || kind > 7 || (n && (!archives || !lens || !outs || !out_lens || !statuses))) return SWC_E_INVALID_ARGUMENT;
     for (size_t i = 0; i < n; i++) if (lens[i] && !archives[i]) return SWC_E_INVALID_ARGUMENT;
-    if (!device_ready()) return SWC_E_DEVICE;
+    // (no device asked for here: a set whose every archive fails in its header launches nothing and is answered on any machine, as
+    // the single-shot calls answer it; the first launch is what reports SWC_E_DEVICE)
     std::vector<Result> res(n);
     const int st = many_dispatch(kind, archives, lens, n, res);
     if (st) return st;
