@@ -4,7 +4,8 @@
 // length parsing, the end-of-block rules the reference enforces (:369-376), offset
 // validation against dictionary + bytes produced (:380-383), and the overlapping match copy
 // (:403-409).  The reference copies one byte per `append`; here literals and matches move 8 bytes per
-// load/store, overlapping matches replicate their `offset`-byte pattern in a register first.
+// load/store, overlapping matches replicate their `offset`-byte pattern in a register first.  A sequence's last bytes go in a
+// four-byte and in single-byte steps: no byte of `out` behind min(out_len, out_cap) is written, on any path.
 //
 // Used for batches of many small blocks (one lane each, 64 blocks per wave).  Large blocks go through
 // the wave-cooperative kernel in lz4_wave.h; both produce identical bytes and statuses.
@@ -46,14 +47,12 @@ SWC_HD void lz4_block_job(Job& job) {
             if (st) break;
         }
         if (n - ip < lit) { st = SWC_E_DATA_TRUNCATED; break; }                    // :363
-        {   // literals: input -> output
+        {   // literals: input -> output, the part of them below the capacity and not a byte more
+            const uint64_t keep = pos >= cap ? 0 : (cap - pos < lit ? cap - pos : lit);
             uint64_t i = 0;
-            if (pos + lit + 8 <= cap && ip + lit + 8 <= n) {
-                for (; i < lit; i += 8) store_u64(out + pos + i, load_u64(in + ip + i));  // may overrun < 8 B inside both buffers
-            } else {
-                for (; i < lit; i++)
-                    if (pos + i < cap) out[pos + i] = in[ip + i];
-            }
+            for (; i + 8 <= keep; i += 8) store_u64(out + pos + i, load_u64(in + ip + i));
+            if (i + 4 <= keep) { store_u32(out + pos + i, load_u32(in + ip + i)); i += 4; }
+            for (; i < keep; i++) out[pos + i] = in[ip + i];
         }
         ip += lit;
         pos += lit;
@@ -90,28 +89,26 @@ SWC_HD void lz4_block_job(Job& job) {
             done = k;
         }
         if (done < mlen) {
-            uint64_t p = pos + done, rem = mlen - done;
-            if (p + rem + 8 <= cap) {
-                uint64_t d = offset;
-                if (d < 8) {
-                    // replicate the d-byte pattern to 8 bytes, then continue at the smallest multiple of d >= 8
-                    uint32_t sh = 8 * (uint32_t)d;
-                    uint64_t w = load_u64(out + p - d) & ((1ull << sh) - 1ull);
-                    w |= w << sh;
-                    sh *= 2;
-                    if (sh < 64) { w |= w << sh; sh *= 2; }
-                    if (sh < 64) w |= w << sh;
-                    store_u64(out + p, w);
-                    const uint64_t k = rem < 8 ? rem : 8;
-                    p += k;
-                    rem -= k;
-                    d = ((7 + d) / d) * d;
-                }
-                for (uint64_t i = 0; i < rem; i += 8) store_u64(out + p + i, load_u64(out + p + i - d));
-            } else {
-                for (uint64_t i = 0; i < rem; i++)
-                    if (p + i < cap) out[p + i] = out[p + i - offset];
+            const uint64_t p = pos + done, left = mlen - done;
+            const uint64_t rem = p >= cap ? 0 : (cap - p < left ? cap - p : left);   // the part below the capacity: not a byte behind it is written
+            uint64_t d = offset, i = 0;
+            if (d < 8 && rem >= 8) {
+                // replicate the d-byte pattern to 8 bytes (the load stays below p + 8 <= p + rem), then continue at the smallest
+                // multiple of d >= 8
+                uint32_t sh = 8 * (uint32_t)d;
+                uint64_t w = load_u64(out + p - d) & ((1ull << sh) - 1ull);
+                w |= w << sh;
+                sh *= 2;
+                if (sh < 64) { w |= w << sh; sh *= 2; }
+                if (sh < 64) w |= w << sh;
+                store_u64(out + p, w);
+                i = 8;
+                d = ((7 + d) / d) * d;
             }
+            if (d >= 8)
+                for (; i + 8 <= rem; i += 8) store_u64(out + p + i, load_u64(out + p + i - d));
+            if (d >= 4 && i + 4 <= rem) { store_u32(out + p + i, load_u32(out + p + i - d)); i += 4; }
+            for (; i < rem; i++) out[p + i] = out[p + i - offset];
         }
         pos += mlen;
     }

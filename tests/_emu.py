@@ -136,11 +136,12 @@ class Guarded:
 
 
 def run_batch(fn_name, inputs, caps, aux=None, dicts=None, extra=None, fn_args=(), dict_ptr_values=None, misalign=0, lib=None,
-              in_misalign=None):
+              in_misalign=None, exact=False):
     """inputs: list[bytes]; caps: list[int].  Returns list of (status, out_bytes, in_consumed, out_len).
     misalign: the output buffers start that many bytes past a 16-byte boundary, 16 guard bytes on either side.  lib: another build
     of the library (ASAN).  in_misalign (not None): the inputs -- and the dictionaries, seven residues further -- lie in guarded
-    buffers of their own that many bytes past a 16-byte boundary, and are checked unchanged afterwards."""
+    buffers of their own that many bytes past a 16-byte boundary, and are checked unchanged afterwards.  exact: the bytes of an output
+    buffer behind the first min(out_len, capacity) count as guard bytes too -- nothing may be written there."""
     n = len(inputs)
     jobs = (Job * n)()
     keep, outs, ins = [], [], []
@@ -175,7 +176,7 @@ def run_batch(fn_name, inputs, caps, aux=None, dicts=None, extra=None, fn_args=(
         buf.check(what)
         assert buf.read() == data, "%s changed" % what
     for i in range(n):
-        outs[i].check("job %d" % i)
+        outs[i].check("job %d" % i, used=min(jobs[i].out_len, caps[i]) if exact else None)
         res.append((jobs[i].status, outs[i].read(0, min(jobs[i].out_len, caps[i])), jobs[i].in_consumed, jobs[i].out_len))
     return res
 
@@ -185,9 +186,9 @@ def inflate(inputs, caps, misalign=0, in_misalign=None):
     return run_batch("emu_inflate_sync", inputs, caps, misalign=misalign, in_misalign=in_misalign)
 
 
-def lz4_block(inputs, caps, dicts=None, misalign=0, in_misalign=None, aux=None):
+def lz4_block(inputs, caps, dicts=None, misalign=0, in_misalign=None, aux=None, exact=False):
     """aux: the swc_lz4_aux bits of every job (SWC_LZ4_STORED = 2: `in` is copied)."""
-    return run_batch("emu_lz4_block", inputs, caps, aux=aux, dicts=dicts, misalign=misalign, in_misalign=in_misalign)
+    return run_batch("emu_lz4_block", inputs, caps, aux=aux, dicts=dicts, misalign=misalign, in_misalign=in_misalign, exact=exact)
 
 
 LZMA_MODE = 0   # 0: literal coders in LDS / cell-by-cell spill (kernel without a workspace); 1: LDS as a cache of four coders

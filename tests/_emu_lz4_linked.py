@@ -12,12 +12,13 @@ set_order = _emu.set_order
 GUARD = 16
 
 
-def run_chains(chains, misalign=0, copier=1):
+def run_chains(chains, misalign=0, copier=1, exact=False):
     """Chains (tests/_lz4_linked_cases.py) as ONE job list through one emulated launch -- copier: 1 = of kCopierMin jobs and more (one
     record-mode parse, the chain copier over all jobs), 0 = a smaller one (the four-kernel split).  Every chain has a buffer of its
     own -- the prefix, then the sum of the capacities -- that starts `misalign` bytes past a 16-byte boundary (the head's `out` where
     the prefix is empty) and has GUARD bytes of 0xA5 on both sides.  Returns per chain the list, per job, of (status, out_len,
-    in_consumed, offset of `out` from the head's, bytes); asserts that the guards and the prefixes are untouched."""
+    in_consumed, offset of `out` from the head's, bytes); asserts that the guards and the prefixes are untouched -- with `exact`, also
+    every byte of the buffer behind the last one a job of the chain reports."""
     n = sum(len(ch["jobs"]) for ch in chains)
     jobs = (Job * n)()
     keep, bufs, i = [], [], 0
@@ -48,15 +49,17 @@ def run_chains(chains, misalign=0, copier=1):
     for ch, buf in zip(chains, bufs):
         prefix = ch["prefix"]
         room, out0 = buf.n - len(prefix), buf.addr + len(prefix)
-        buf.check(ch["name"])
         assert buf.read(0, len(prefix)) == prefix, "prefix overwritten"
-        res = []
+        res, end = [], len(prefix)
         for _ in ch["jobs"]:
             rel = (jobs[i].out or 0) - out0
             k = min(jobs[i].out_len, jobs[i].out_cap)
             at = len(prefix) + rel
+            if 0 <= rel <= room:
+                end = max(end, min(at + k, buf.n))
             res.append((jobs[i].status, jobs[i].out_len, jobs[i].in_consumed, rel, buf.read(at, min(at + k, buf.n)) if 0 <= rel <= room else None))
             i += 1
+        buf.check(ch["name"], used=end if exact else None)
         out.append(res)
     return out
 
