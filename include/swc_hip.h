@@ -55,10 +55,23 @@ typedef enum swc_codec {
                               aligned; A valid stream for the same bytes, not the reference's bytes.  aux bit 0:
                               the unit is a SEGMENT of a longer stream -- BFINAL clear, an empty stored block behind the block, so
                               that the outputs of consecutive segments, the last one with aux = 0, are one stream           */
-    SWC_CODEC_DEFLATE_COMPRESS_DYNAMIC = 9 /* ENCODE, the job contract of 8 (the same parse, out_cap, alignment and aux bit 0); the
+    SWC_CODEC_DEFLATE_COMPRESS_DYNAMIC = 9, /* ENCODE, the job contract of 8 (the same parse, out_cap, alignment and aux bit 0); the
                               block is dynamic-Huffman (BTYPE 10, its own code tables, 15-bit codes) where that is strictly
                               smaller than the static block, and stored when not larger than the better of the two (an
                               extension: the reference writes no dynamic block).  Where it is not dynamic, the bytes of 8  */
+    SWC_CODEC_LZMA2_COMPRESS = 10 /* ENCODE, one LZMA2 RUN (an extension: the reference has no LZMA encoder): in = the
+                              unit, written by one wavefront as chunks of 65,536 bytes -- LZMA (lc 3, lp 0, pb 2, distances up to
+                              65,535: dictionary-size byte 8) or stored, whichever is smaller -- behind a dictionary reset, the
+                              end marker 0x00 behind the last; out_cap >= n + 3 ceil(n / 65536) + 1, in and out at any alignment.
+                              A valid stream for LZMA2Decoder.decode() (LZMA2Decoder.swift:36-74), liblzma and SWC_CODEC_LZMA2.
+                              aux bit 0: the unit is a SEGMENT of a longer stream -- no end marker, so that the outputs of
+                              consecutive segments, the last one with aux = 0, are one stream.  A CORRECTNESS condition of the
+                              bit: the encoder counts positions (pos_state) from the start of its unit, as liblzma does behind
+                              a dictionary reset; LZMA2Decoder.decode() and SWC_CODEC_LZMA2 count from the start of the stream.
+                              So every segment with a successor must be a multiple of 4 bytes long -- behind one that is not,
+                              the joined stream decodes under liblzma only, unless every later chunk up to the next multiple
+                              of 4 happens to be stored.  Multiples of 16 make the segments the units that SWC_LZMA2_OPEN
+                              and swc_index_blocks kind 8 cut again  */
 } swc_codec;
 
 /* aux of an SWC_CODEC_LZ4_BLOCK job (0: an independent block, as ever).  With either bit the launch needs the workspace
@@ -241,6 +254,11 @@ int swc_lzma_alone_decompress(const uint8_t* in, size_t in_len, uint8_t** out, s
 int swc_lzma2_decompress(const uint8_t* in, size_t in_len, uint8_t dict_byte, uint8_t** out, size_t* out_len, size_t* in_consumed);
 /* LZMA2.decompress(data:) LZMA2.swift:25-30 (first byte = dictionary size) */
 int swc_lzma2_decompress_data(const uint8_t* in, size_t in_len, uint8_t** out, size_t* out_len);
+/* LZMA2.compress(data:) -- an extension, the reference writes no LZMA2: the dictionary-size byte (8) followed by the stream, which
+ * is what swc_lzma2_decompress_data takes.  Compressed on the device (SWC_CODEC_LZMA2_COMPRESS; one wavefront per buffer of up to
+ * 1 MiB; a larger one is cut into segments of 256 KiB that are compressed in one launch and come out as runs behind dictionary
+ * resets -- one LZMA2 stream, which "lzma2_run_bytes" decodes as parallel units).  Empty input: 08 00. */
+int swc_lzma2_compress(const uint8_t* data, size_t len, uint8_t** out, size_t* out_len);
 
 /* LZ4.decompress(data:dictionary:dictionaryID:) LZ4.swift:73-91; dict NULL = no dictionary,
  * dict_id < 0 = no id passed; *out valid on SWC_E_DATA_CHECKSUM_MISMATCH */
@@ -330,6 +348,14 @@ int swc_zlib_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, size_t* 
 /* XZArchive.unarchive(archive:) XZArchive.swift:27-51 / splitUnarchive :69-88 */
 int swc_xz_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, size_t* out_len);
 int swc_xz_split_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, size_t* out_len, size_t** sizes, size_t* n_streams);
+/* XZArchive.archive(data:) -- an extension, the reference writes no .xz: ONE stream -- the stream header, one block per block_size
+ * bytes of data (0: 262,144; else a multiple of 16 in 4,096 .. 2^30), the index, the footer.  A block's header carries flags 0xC0,
+ * both size fields and the LZMA2 filter with dictionary-size byte 8 (the layout of a multi-threaded xz, which readers split by);
+ * its data are one SWC_CODEC_LZMA2_COMPRESS run.  All blocks are compressed in ONE launch; their checks (check_type 0 none,
+ * 1 CRC-32, 4 CRC-64, 10 SHA-256; anything else SWC_E_INVALID_ARGUMENT) are taken on the device over the staged data (SHA-256: from
+ * "sha256_device_min_units" blocks on, below that by swc_sha256); the CRC-32s of the headers, the index and the footer on the host.
+ * Empty data: the 32-byte archive without a block, answered without a device. */
+int swc_xz_archive(const uint8_t* data, size_t len, int check_type, size_t block_size, uint8_t** out, size_t* out_len);
 
 /* Many independent archives in one call: host-side block discovery + ONE batched launch.
  * archives[i]/lens[i] are host buffers; outs[i]/out_lens[i]/statuses[i] are filled per archive

@@ -338,6 +338,12 @@ class LZMA2:
         """(output, consumed) -- LZMA2.decompress(_:_:) LZMA2.swift:32."""
         return _call_simple("swc_lzma2_decompress", data, dict_byte, consumed=True)
 
+    @staticmethod
+    def compress(data):
+        """The dictionary-size byte (8) and the stream -- what LZMA2.decompress takes; compressed on the device (an extension: the
+        reference has no LZMA2 encoder)."""
+        return _call_simple("swc_lzma2_compress", data)
+
 
 class XZArchive:
     @staticmethod
@@ -347,6 +353,14 @@ class XZArchive:
     @staticmethod
     def split_unarchive(archive):
         return _call_multi("swc_xz_split_unarchive", archive)
+
+    CHECKS = {"none": 0, "crc32": 1, "crc64": 4, "sha256": 10}
+
+    @staticmethod
+    def archive(data, check="crc64", block_size=262144):
+        """One .xz stream of independent blocks of `block_size` bytes, compressed in one launch, the blocks' checks ('none' | 'crc32'
+        | 'crc64' | 'sha256', or the check's number) taken on the device (an extension: the reference writes no .xz)."""
+        return _call_simple("swc_xz_archive", data, XZArchive.CHECKS.get(check, check), C.c_size_t(block_size))
 
 
 class LZ4:

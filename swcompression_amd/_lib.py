@@ -78,6 +78,8 @@ def load():
     sig("swc_lz4_decompress", I, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int64, u8pp, szp, szp)
     sig("swc_lz4_multi_decompress", I, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int64, u8pp, szp, szpp, szp)
     sig("swc_deflate_compress", I, C.c_char_p, C.c_size_t, u8pp, szp)
+    sig("swc_lzma2_compress", I, C.c_char_p, C.c_size_t, u8pp, szp)
+    sig("swc_xz_archive", I, C.c_char_p, C.c_size_t, C.c_int, C.c_size_t, u8pp, szp)
     sig("swc_bzip2_compress", I, C.c_char_p, C.c_size_t, I, u8pp, szp)
     sig("swc_zlib_archive", I, C.c_char_p, C.c_size_t, u8pp, szp)
     sig("swc_deflate_compress_dynamic", I, C.c_char_p, C.c_size_t, u8pp, szp)

@@ -89,6 +89,7 @@ static hipError_t launch_codec(int codec, Job* jobs, size_t n, void* ws, size_t 
         case SWC_CODEC_LZ4_COMPRESS: return launch_lz4_compress(jobs, n, stream);
         case SWC_CODEC_DEFLATE_COMPRESS: return launch_deflate_compress(jobs, n, stream);
         case SWC_CODEC_DEFLATE_COMPRESS_DYNAMIC: return launch_deflate_compress_dynamic(jobs, n, stream);
+        case SWC_CODEC_LZMA2_COMPRESS: return launch_lzma2_compress(jobs, n, stream);
         default: return hipErrorInvalidValue;
     }
 }
@@ -305,6 +306,11 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
             out_off[k] = out_total + adj;
             out_total += adj + ((cap[pending[k]] + 15) & ~(size_t)15);
         }
+        // checksums of the units' INPUT (HostUnit::sum_of_input): a second job list behind the inputs whose "outputs" are the inputs
+        bool sum_in = false;
+        for (size_t k = 0; k < m; k++) sum_in = sum_in || (units[pending[k]].sum_kind && units[pending[k]].sum_of_input);
+        const size_t view_off = in_total;
+        if (sum_in) in_total += (m * sizeof(Job) + 15) & ~(size_t)15;
         // workspace: per-job areas (prefix-summed) where the codec sizes them from the capacity, else one size for all
         std::vector<uint64_t> ws_off;
         size_t ws_bytes = 0;
@@ -364,7 +370,15 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
             j.aux = u.aux;
             j.dict = u.dict ? (u.dict_adjacent ? d_out + out_off[k] - u.dict_len : d_in + dict_off[k]) : reinterpret_cast<const uint8_t*>((uintptr_t)u.dict_value);
             j.dict_len = u.dict ? u.dict_len : u.extra;
+            if (sum_in) {
+                Job& v = reinterpret_cast<Job*>(up + view_off)[k];
+                v = j;
+                v.out = const_cast<uint8_t*>(j.in);
+                v.out_cap = v.out_len = j.in_len;
+                v.status = SWC_OK;
+            }
         }
+        const Job* sum_jobs = sum_in ? reinterpret_cast<const Job*>(d_in + view_off) : reinterpret_cast<const Job*>(d_jobs);
         if (!ws_off.empty()) memcpy(up + in_bytes + jobs_bytes, ws_off.data(), ws_off.size() * sizeof(uint64_t));
         tr.mark("stage inputs (pinned)", up_bytes);
         if (hipMemcpyAsync(d_in, up, up_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return SWC_E_DEVICE;
@@ -382,8 +396,8 @@ static int run_units_impl(int codec, std::vector<HostUnit>& units) {
         } else {
             if (launch_codec(codec, reinterpret_cast<Job*>(d_jobs), m, d_ws.ptr(), ws_bytes, stream, d_off) != hipSuccess) return SWC_E_DEVICE;
             if (sum_kind == kSumSha256) {
-                if (launch_sha256(reinterpret_cast<const Job*>(d_jobs), m, d_sums, stream) != hipSuccess) return SWC_E_DEVICE;
-            } else if (sum_kind && launch_checksum(sum_kind, reinterpret_cast<const Job*>(d_jobs), m, reinterpret_cast<uint64_t*>(d_sums), stream) != hipSuccess) return SWC_E_DEVICE;
+                if (launch_sha256(sum_jobs, m, d_sums, stream) != hipSuccess) return SWC_E_DEVICE;
+            } else if (sum_kind && launch_checksum(sum_kind, sum_jobs, m, reinterpret_cast<uint64_t*>(d_sums), stream) != hipSuccess) return SWC_E_DEVICE;
         }
         stat_add(kStatLaunches, 1);
         stat_add(kStatUnits, (long long)m);

@@ -9,6 +9,7 @@
 //   DeltaFilter.decode      reference Sources/Common/DeltaFilter.swift:11-33
 // Headers, index, footer, padding and checks are verified on the host; every LZMA2 block body is a
 // unit of the batched device launch.
+//   LZMA2.compress(data:) / XZArchive.archive(data:)   extensions: the runs of lzma_comp.h, framed on the host
 #include <algorithm>
 #include <atomic>
 #include <map>
@@ -670,6 +671,42 @@ const RunCodec& lzma2_runs() {
     return c;
 }
 
+// ---- the write side: LZMA2.compress and XZArchive.archive (extensions: the reference writes neither) ------------------------------
+// One run per unit (SWC_CODEC_LZMA2_COMPRESS, lzma_comp.h): a buffer of up to kCompressWhole bytes is one unit; a larger one is
+// cut into segments of kCompressSegment bytes, one wavefront each, all in one launch -- the rule of swc_deflate_compress.  Every
+// segment but the last is a SEGMENT (job.aux bit 0: no end marker); one behind the other they are one LZMA2 stream whose
+// dictionary resets are the cuts that "lzma2_run_bytes" decodes in parallel (the segments are multiples of 16 bytes).
+namespace {
+constexpr size_t kCompressWhole = (size_t)1 << 20, kCompressSegment = (size_t)256 << 10;
+constexpr uint8_t kCompressDictByte = 8;   // lzma_comp.h: distances of up to 65,535
+size_t lzma2_bound(size_t n) { return n + 3 * ((n + 65535) / 65536) + 1; }
+
+// data as units of `seg` bytes (0: one unit); sum_kind: the units' check of their INPUT, from the device
+void lzma2_compress_units(const uint8_t* data, size_t len, size_t seg, bool all_final, int sum_kind, std::vector<HostUnit>& units) {
+    const size_t nseg = seg ? (len + seg - 1) / seg : 1;
+    units.resize(nseg);
+    for (size_t k = 0; k < nseg; k++) {
+        HostUnit& s = units[k];
+        const size_t lo = seg ? k * seg : 0, n = seg ? std::min(seg, len - lo) : len;
+        s.in = data + lo; s.in_len = n;
+        s.base = data; s.base_len = len;            // one staged copy of the buffer, every unit a sub-range of it
+        s.cap_hint = lzma2_bound(n);
+        s.cap_exact = true;
+        s.aux = all_final || k + 1 == nseg ? 0 : 1;
+        s.sum_kind = sum_kind;
+        s.sum_of_input = sum_kind != 0;
+    }
+}
+
+void put_vli(std::vector<uint8_t>& v, uint64_t x) {
+    while (x >= 0x80) { v.push_back((uint8_t)(x | 0x80)); x >>= 7; }
+    v.push_back((uint8_t)x);
+}
+void put_le32(std::vector<uint8_t>& v, uint32_t x) { for (int i = 0; i < 4; i++) v.push_back((uint8_t)(x >> (8 * i))); }
+void pad4(std::vector<uint8_t>& v, size_t from) { while ((v.size() - from) & 3) v.push_back(0); }
+int xz_check_size(int check_type) { return check_type == 0 ? 0 : check_type == 1 ? 4 : check_type == 4 ? 8 : 32; }
+}  // namespace
+
 }  // namespace swc
 
 using namespace swc;
@@ -766,6 +803,93 @@ int swc_xz_split_unarchive(const uint8_t* in, size_t in_len, uint8_t** out, size
     if (out && out_len) give_empty(out, out_len);
     if (sizes) *sizes = nullptr;
     if (n_streams) *n_streams = 0;
+    return SWC_E_DEVICE;
+}
+
+int swc_lzma2_compress(const uint8_t* data, size_t len, uint8_t** out, size_t* out_len) try {
+    if (!out || !out_len || (len && !data)) return SWC_E_INVALID_ARGUMENT;
+    std::vector<HostUnit> units;
+    lzma2_compress_units(data, len, len > kCompressWhole ? kCompressSegment : 0, false, 0, units);
+    int st = run_units(SWC_CODEC_LZMA2_COMPRESS, units);
+    for (const HostUnit& u : units) if (st == SWC_OK) st = u.status;
+    if (st) { give_empty(out, out_len); return st; }
+    std::vector<uint8_t> res;
+    size_t total = 1;
+    for (const HostUnit& u : units) total += u.size();
+    res.reserve(total);
+    res.push_back(kCompressDictByte);
+    for (const HostUnit& u : units) res.insert(res.end(), u.data(), u.data() + u.size());
+    give(res, out, out_len);
+    return SWC_OK;
+} catch (...) {
+    if (out && out_len) give_empty(out, out_len);
+    return SWC_E_DEVICE;
+}
+
+int swc_xz_archive(const uint8_t* data, size_t len, int check_type, size_t block_size, uint8_t** out, size_t* out_len) try {
+    if (!out || !out_len || (len && !data)) return SWC_E_INVALID_ARGUMENT;
+    if (check_type != 0 && check_type != 1 && check_type != 4 && check_type != 10) return SWC_E_INVALID_ARGUMENT;
+    if (block_size == 0) block_size = kCompressSegment;
+    if (block_size < 4096 || block_size > ((size_t)1 << 30) || (block_size & 15)) return SWC_E_INVALID_ARGUMENT;
+    // the blocks: every one a whole run with its end marker, in ONE launch; their checks over the staged input behind it
+    std::vector<HostUnit> units;
+    const size_t nblocks = (len + block_size - 1) / block_size;
+    const int kind = xz_sum_kind(check_type, nblocks);
+    if (len) {   // (an empty archive has no block and needs no device)
+        lzma2_compress_units(data, len, block_size, true, kind, units);
+        int st = run_units(SWC_CODEC_LZMA2_COMPRESS, units);
+        for (const HostUnit& u : units) if (st == SWC_OK) st = u.status;
+        if (st) { give_empty(out, out_len); return st; }
+    }
+    const int csize = xz_check_size(check_type);
+    std::vector<uint8_t> a;
+    size_t total = 64 + 20 * nblocks;
+    for (const HostUnit& u : units) total += u.size() + 64;
+    a.reserve(total);
+    const uint8_t magic[6] = {0xFD, '7', 'z', 'X', 'Z', 0x00}, flags[2] = {0, (uint8_t)check_type};
+    a.insert(a.end(), magic, magic + 6);
+    a.insert(a.end(), flags, flags + 2);
+    put_le32(a, swc_crc32(flags, 2, 0));
+    std::vector<uint8_t> index;
+    index.push_back(0);
+    put_vli(index, nblocks);
+    for (const HostUnit& u : units) {
+        const size_t start = a.size();
+        a.push_back(0);                            // header size, filled in below
+        a.push_back(0xC0);                         // both sizes, one filter: what a threaded reader needs to split the file
+        put_vli(a, u.size());
+        put_vli(a, u.in_len);
+        a.push_back(0x21); a.push_back(1); a.push_back(kCompressDictByte);
+        pad4(a, start);
+        a[start] = (uint8_t)((a.size() - start + 4) / 4 - 1);
+        put_le32(a, swc_crc32(a.data() + start, a.size() - start, 0));
+        const size_t header = a.size() - start;
+        a.insert(a.end(), u.data(), u.data() + u.size());
+        pad4(a, start);
+        if (check_type == 1) put_le32(a, u.sum_valid ? (uint32_t)u.sum : swc_crc32(u.in, u.in_len, 0));
+        else if (check_type == 4) { const uint64_t c = u.sum_valid ? u.sum : swc_crc64(u.in, u.in_len); put_le32(a, (uint32_t)c); put_le32(a, (uint32_t)(c >> 32)); }
+        else if (check_type == 10) {
+            uint8_t dg[32];
+            if (u.sum_valid) { memcpy(dg, u.digest, 32); stat_add(kStatSha256DeviceUnits, 1); }
+            else swc_sha256(u.in, u.in_len, dg);   // (fewer than "sha256_device_min_units" blocks)
+            a.insert(a.end(), dg, dg + 32);
+        }
+        put_vli(index, header + u.size() + (size_t)csize);   // the unpadded size
+        put_vli(index, u.in_len);
+    }
+    pad4(index, 0);
+    put_le32(index, swc_crc32(index.data(), index.size(), 0));
+    a.insert(a.end(), index.begin(), index.end());
+    std::vector<uint8_t> tail;
+    put_le32(tail, (uint32_t)(index.size() / 4 - 1));
+    tail.insert(tail.end(), flags, flags + 2);
+    put_le32(a, swc_crc32(tail.data(), tail.size(), 0));
+    a.insert(a.end(), tail.begin(), tail.end());
+    a.push_back('Y'); a.push_back('Z');
+    give(a, out, out_len);
+    return SWC_OK;
+} catch (...) {
+    if (out && out_len) give_empty(out, out_len);
     return SWC_E_DEVICE;
 }
 

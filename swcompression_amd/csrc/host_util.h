@@ -97,6 +97,9 @@ struct HostUnit {
     // include/swc_hip.h: 1 CRC-32, 2 Adler-32, 3 CRC-64, 4 bzip2 CRC-32, 5 XXH32; kSumSha256, internal: SHA-256, swc_batch_sha256's
     // kernel); one kind per run_units call.
     int sum_kind = 0;
+    // ... of the unit's INPUT instead (the encoders: the check of an .xz block is of what went in): taken over a view of the staged
+    // input; all units of a call that ask for a checksum agree on this
+    bool sum_of_input = false;
     // results
     std::vector<uint8_t> out;
     bool in_dst = false;         // the output is at `dst`, not in `out`

@@ -22,6 +22,7 @@
 #include "lz4_chain.h"
 #include "lz4_comp.h"
 #include "deflate_comp.h"
+#include "lzma_comp.h"
 #include "lzma_wave.h"
 #include "bzip2_block.h"
 #include "bzip2_team.h"
@@ -276,6 +277,14 @@ template <int WAVE>
 SWC_D void deflate_compress_dynamic(Job* __restrict__ jobs, uint32_t g, defc::DynLds* lds, int lane) {
     Job job = jobs[g];
     defc::deflate_compress_dynamic_job<WAVE>(job, lds);
+    if (lane == 0) put_result(jobs, g, job);
+}
+
+// swc_lzma2_compress_kernel (lzma_compress.hip)
+template <int WAVE>
+SWC_D void lzma2_compress(Job* __restrict__ jobs, uint32_t g, lzmac::Lds* lds, int lane) {
+    Job job = jobs[g];
+    lzmac::lzma2_compress_job<WAVE>(job, lds);
     if (lane == 0) put_result(jobs, g, job);
 }
 

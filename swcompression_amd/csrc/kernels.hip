@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void swc_order_scatter_kernel(const Job* __res
     if (g < n) perm[base[c] + r] = g;
 }
 // device buffer of the calling thread for the order of one launch on `stream` (perm[n] | cursors), or nullptr
-static const uint32_t* job_order(const Job* jobs, size_t n, hipStream_t stream, bool chains = false) {
+const uint32_t* job_order(const Job* jobs, size_t n, hipStream_t stream, bool chains) {
     if (n < kOrderMin) return nullptr;
     struct Buf { hipStream_t s; int dev; uint32_t* p; size_t cap; };
     static thread_local std::vector<Buf> bufs;   // (never freed: a few hundred KB per launching thread and stream)

@@ -1,4 +1,5 @@
-// launch.h -- host-side launch wrappers implemented in kernels.hip (launch_inflate_team: inflate_team.hip): which kernels, in which
+// launch.h -- host-side launch wrappers implemented in kernels.hip (launch_inflate_team: inflate_team.hip; launch_lzma2_compress:
+// lzma_compress.hip): which kernels, in which
 // order, with which flags.  What a kernel does with its job is in job_kernels.h.
 #ifndef SWC_LAUNCH_H
 #define SWC_LAUNCH_H
@@ -28,9 +29,14 @@ void set_bzip2_team_walk(int v);
 int last_phase_ms(float* ms, int cap);
 hipError_t launch_lz4(Job* jobs, size_t n, void* ws, size_t ws_bytes, hipStream_t stream, const uint64_t* ws_off = nullptr);
 size_t lz4_ws_bytes_per_job(uint64_t cap);
+// the launch order of a batch on `stream` (kernels.hip: longest jobs first): perm[b] = the job of workgroup b, nullptr = the plain
+// XCD-aware order of xcd_job
+const uint32_t* job_order(const Job* jobs, size_t n, hipStream_t stream, bool chains = false);
 hipError_t launch_lz4_compress(Job* jobs, size_t n, hipStream_t stream);
 hipError_t launch_deflate_compress(Job* jobs, size_t n, hipStream_t stream);
 hipError_t launch_deflate_compress_dynamic(Job* jobs, size_t n, hipStream_t stream);
+// lzma_compress.hip: one LZMA2 run per wavefront (lzma_comp.h)
+hipError_t launch_lzma2_compress(Job* jobs, size_t n, hipStream_t stream);
 // bgzf_pack.h: the whole BGZF writer on `stream` (set-up, one compress launch, CRC-32, offsets, pack); `ws`: 16-byte aligned device
 // memory of bgzf::plan(len, bs).bytes, the Result at its plan().res; eof: the end-of-file member behind the last one
 hipError_t launch_bgzf_archive(const uint8_t* src, uint64_t len, uint32_t bs, bool dynamic, uint8_t* dst, uint64_t dst_cap, uint64_t* total,
